@@ -2,14 +2,23 @@
 """bench.py -- the kvpress score -> top-k -> gather hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload snapkv128k|knorm32k|knorm128k|ea128k|<f-row workload>]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is ONE pass of the hot path over one batch of synthetic input: one layer's
 ``press.compress()`` (score + top-k + gather) for B=1 per GPU, Llama-3.1-8B attention geometry
 (H_q=32, H_kv=8, D=128, hidden 4096, bf16, llama3 RoPE), inputs resident in HBM.
 Default workload = BASELINE.json's metric configuration (configs[2]): SnapKVPress(0.5), S=131072.
 
+A plain run sets up, pre-warms, runs the W warm-up and the K timed steps, writes the outputs of the last timed step if
+``--dump-outputs`` is given, and prints the result line; ``roofline`` and ``cpu_baseline`` are null there.  Everything below
+the metric (roofline, the profiler passes, hipEvent steps, fixture parity, CPU baseline, ``extra``) runs with ``--full`` only.
+
 metric  : press ms/layer (``ms_per_step``) and press-only prefill tok/s (``value`` =
           n_gpus * S / (32 layers * t_layer)), as BASELINE.json / SURVEY.md §8(d) define them.
+outputs : ``--dump-outputs DIR`` writes K', V' of the last timed step (what a caller of ``press.compress()`` receives) as float32
+          DIR/keys.npy, DIR/values.npy (DIR/keys_rank<r>.npy ... with N > 1): whole when they fit, otherwise the same seeded
+          sample of rows (kept positions) of every (batch element, head), at most DUMP_BYTES in all.  The inputs are seeded, so
+          two builds run with the same arguments can be compared output for output.
 roofline: the dominant library kernel (largest average duration), its algorithmic bytes / duration vs the 8 TB/s HBM
           peak.  Kernel durations are rocprofv3's: the run spawns one `rocprofv3 --kernel-trace` pass around a child run of the
           same workload and averages every kernel's dispatches from its rocpd database (what profiles/rNN_rocprofv3_kernel_stats_*.csv
@@ -80,6 +89,7 @@ ROUND = "r06"   # prefix of the committed profiles/ this build's fallbacks read
 # whose retained sets are pinned to the real reference (tests/golden/full_snapkv128k.npz, full_knorm32k.npz)
 SEEDS = {"snapkv128k": 103, "snapkv128k_scoreorder": 103, "snapkv128k_b2": 103, "knorm32k": 102, "ea128k": 104}
 FIXTURES = {"snapkv128k": "full_snapkv128k", "knorm32k": "full_knorm32k", "ea128k": "full_ea128k_A"}   # reference outputs for exactly the timed tensors
+DUMP_BYTES = 48 << 20   # --dump-outputs: bytes of all .npy files together (all ranks)
 
 
 def shard_batch(global_batch: int, world: int, rank: int):
@@ -259,7 +269,7 @@ def live_pmc_traffic(kernel_name: str, workload: str, timeout_s: float = 240.0):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, counter)
             cmd = [exe, "--kernel-trace", "--pmc", counter, "-d", out, "-o", "pmc", "--", sys.executable, os.path.join(ROOT, "bench.py"),
-                   "--workload", workload, "--steps", "3", "--warmup", "1", "--prewarm-ms", "5", "--no-cpu-baseline"]
+                   "--workload", workload, "--steps", "3", "--warmup", "1", "--prewarm-ms", "5", "--no-cpu-baseline", "--full"]
             try:
                 r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=max(30.0, timeout_s - (time.perf_counter() - t0)))
             except (subprocess.TimeoutExpired, OSError) as e:
@@ -345,7 +355,7 @@ def live_kernel_trace(names, workload: str, timeout_s: float = 240.0, csv_path=N
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     t0 = time.perf_counter()
-    child = ["--workload", workload, "--steps", "100", "--warmup", "10", "--prewarm-ms", "60", "--no-cpu-baseline"]
+    child = ["--workload", workload, "--steps", "100", "--warmup", "10", "--prewarm-ms", "60", "--no-cpu-baseline", "--full"]
     with tempfile.TemporaryDirectory(dir="/tmp", prefix="kvp_trace_") as tmp:
         cmd = [exe, "--kernel-trace", "-d", tmp, "-o", "trace", "--", sys.executable, os.path.join(ROOT, "bench.py"), *child]
         try:
@@ -442,8 +452,9 @@ def launcher_argv(n_gpus: int, argv: list) -> list:
             "--master-port", str(port), os.path.abspath(__file__), *argv]
 
 
-def timed_steps(step, steps: int, warmup: int, world: int, sync) -> float:
-    """W untimed steps, then EXACTLY `steps` steps bracketed by barrier + device sync on both sides; returns this rank's seconds."""
+def timed_steps(step, steps: int, warmup: int, world: int, sync):
+    """W untimed steps, then EXACTLY `steps` steps bracketed by barrier + device sync on both sides; returns (this rank's seconds,
+    what the last timed step returned)."""
     for _ in range(warmup):
         step()
     sync()
@@ -453,12 +464,30 @@ def timed_steps(step, steps: int, warmup: int, world: int, sync) -> float:
         dist.barrier()
     sync()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1):
         step()
+    out = step()   # only the last result is kept: every earlier output is freed before the next step allocates its own
     sync()
     if world > 1:
         dist.barrier()
-    return time.perf_counter() - t0
+    return time.perf_counter() - t0, out
+
+
+def dump_outputs(out_dir: str, out, world: int, rank: int) -> None:
+    """--dump-outputs: K', V' [B, H_kv, n_kept, D] of the last timed step as float32 .npy; when they exceed this rank's share of
+    DUMP_BYTES, the same seeded sample of n_kept rows (sorted, identical for every batch element and head) from each."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    for name, t in zip(("keys", "values"), out):
+        B, H, n, Dh = t.shape
+        rows = min(n, DUMP_BYTES // (len(out) * world) // (B * H * Dh * 4))
+        if rows < n:
+            idx = np.sort(np.random.default_rng(0).choice(n, size=rows, replace=False))
+            t = t.index_select(2, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), t.float().cpu().numpy())
 
 
 def event_timed_steps(step, n: int = 20, warmup: int = 3) -> dict:
@@ -710,7 +739,7 @@ def stub_main(args, world: int, rank: int):
             raise RuntimeError(f"stub failure on rank {rank} (tests: a rank that dies mid-run must take the job down, not hang it)")
         time.sleep(args.stub_step * 1e-3 * (1 + rank))
 
-    local = timed_steps(step, args.steps, args.warmup, world, lambda: None)
+    local, _ = timed_steps(step, args.steps, args.warmup, world, lambda: None)
     t_step = aggregate_time(local, world) / args.steps
     if rank == 0:
         cfg = bench_config(args.workload, world, B, n_kept_of(kind, S, ratio), args.prewarm_ms, "none (stub)", "position", False)
@@ -731,9 +760,15 @@ def main():
     ap.add_argument("--prewarm-ms", type=float, default=60.0,
                     help="untimed device pre-warm before the W warm-up steps: repeat the step for this long so that the clocks have "
                          "ramped (they take ~100 steps; with a short warm-up the same build reads 10 %% slower)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: hipEvent steps, per-kernel table and roofline (with live rocprofv3 passes), fixture parity, "
+                         "CPU baseline and the `extra` block; a plain run times the steps and prints the line, nothing else")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write K', V' of the last timed step as float32 DIR/keys.npy, DIR/values.npy (a fixed seeded sample of rows when "
+                         f"larger than {DUMP_BYTES >> 20} MiB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the `extra` block of the default run (Knorm 32k and ExpectedAttention 128k measured after the headline, ~25 s)")
+                    help="skip the `extra` block of a --full run (Knorm 32k and ExpectedAttention 128k measured after the headline, ~25 s)")
     ap.add_argument("--live-pmc", default="auto", choices=["auto", "off"],
                     help="roofline.traffic: auto = measure it now with two rocprofv3 --pmc passes around a 3-step child run (N = 1, ~40 s); "
                          "off = quote the committed summary of this build (profiles/<round>_pmc_summary_<workload>.txt)")
@@ -750,6 +785,10 @@ def main():
                     help="seconds after which a collective (the barriers around the timed region, the MAX-reduce of the step time) gives up: "
                          "a rank that died must end the job, not leave the others waiting at a barrier")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full and (args.profile_json or args.trace_stats_csv):
+        ap.error("--profile-json and --trace-stats-csv need --full")
 
     # ---- `python bench.py --gpus N`, no launcher around it: become N ranks (one process per GPU, torch.distributed.run) ----
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -818,16 +857,16 @@ def run(args, world: int, rank: int, device, stub: bool):
     lo, hi = shard_batch(world * bpg, world, rank)  # global batch = BATCH[workload] (default one) elements per GPU (weak scaling)
     head = measure(args.workload, args.steps, args.warmup, args.prewarm_ms, world, rank, lo, hi, device, args.live_pmc, args.profile_json,
                    cpu=(rank == 0 and world == 1 and not args.no_cpu_baseline), parity=(rank == 0 and world == 1),   # (N > 1: timing only)
-                   trace_csv=args.trace_stats_csv)
+                   trace_csv=args.trace_stats_csv, full=args.full, dump_dir=args.dump_outputs)
     # ---- BASELINE.json's other single-GPU configurations, measured in the SAME run so that the driver's record carries them
     # (VERDICT r3 #7): config 2 (Knorm 32k) and config 4 (ExpectedAttention 128k).  After the headline's timed region; N = 1 only.
     extra = None
-    if (rank == 0 and world == 1 and args.workload == "snapkv128k" and not args.no_extra and os.environ.get("KVP_BENCH_CHILD") != "1"
+    if (args.full and rank == 0 and world == 1 and args.workload == "snapkv128k" and not args.no_extra and os.environ.get("KVP_BENCH_CHILD") != "1"
             and not under_profiler()):
         extra = {}
         for wl, (st, wu) in (("knorm32k", (200, 20)), ("ea128k", (10, 2))):
             try:
-                r = measure(wl, st, wu, 30.0, 1, 0, 0, 1, device, "off", None, cpu=False, parity=(wl in FIXTURES))
+                r = measure(wl, st, wu, 30.0, 1, 0, 0, 1, device, "off", None, cpu=False, parity=(wl in FIXTURES), full=True)
                 rf = r["roofline"] or {}
                 path = rf.get("path", {})
                 ab = algorithmic_bytes(*WORKLOADS[wl])
@@ -847,8 +886,9 @@ def run(args, world: int, rank: int, device, stub: bool):
                   else f"press ms/layer + prefill tok/s, Llama-3.1-8B, {args.workload}")
         cfg = bench_config(args.workload, world, head["B"], head["n_kept"], args.prewarm_ms, head["inputs"], head["kept_order"], bool(_native.USE_LIBRARY_QPROJ))
         line = result_line(args, world, head["B"], S, head["t_step"], cfg, head["roofline"], head["cpu"], metric)
-        line["parity"] = head["parity"]
-        line["step_events"] = head["step_events"]   # hipEvent median / min per step; ms_per_step above stays the host-clock mean
+        if args.full:
+            line["parity"] = head["parity"]
+            line["step_events"] = head["step_events"]   # hipEvent median / min per step; ms_per_step above stays the host-clock mean
         if extra is not None:
             line["extra"] = extra
         print(json.dumps(line), flush=True)
@@ -898,9 +938,11 @@ def fixture_parity(workload, press, att, hidden, keys, values, kwargs, n_kept):
         return {"fixture": f"tests/golden/{name}.npz", "ok": False, "error": str(e)[:300]}
 
 
-def measure(workload, steps, warmup, prewarm_ms, world, rank, lo, hi, device, live_pmc, profile_json, cpu: bool, parity: bool, trace_csv=None) -> dict:
+def measure(workload, steps, warmup, prewarm_ms, world, rank, lo, hi, device, live_pmc, profile_json, cpu: bool, parity: bool, trace_csv=None,
+            full: bool = False, dump_dir=None) -> dict:
     """One workload on this rank's shard: inputs, pre-warm, W warm-up + K timed steps (barrier + sync bracketed, MAX over ranks),
-    then -- outside the timed region -- per-kernel HIP-event timing, the roofline block, the fixture parity check and the CPU baseline."""
+    the outputs of the last timed step to `dump_dir`, then -- `full` only, outside the timed region -- hipEvent steps, per-kernel
+    HIP-event timing, the roofline block, the fixture parity check and the CPU baseline."""
     import torch
 
     from kvpress_amd import _native
@@ -928,19 +970,19 @@ def measure(workload, steps, warmup, prewarm_ms, world, rank, lo, hi, device, li
         for _ in range(25):
             out = step()
         torch.cuda.synchronize()
-    local = timed_steps(step, steps, warmup, world, torch.cuda.synchronize)
-    out = step()
-    torch.cuda.synchronize()
+    local, out = timed_steps(step, steps, warmup, world, torch.cuda.synchronize)
     _native.async_error_check()   # a select kernel that gave up during the timed region would have poisoned its result: fail, loudly
-    ev_stats = event_timed_steps(step) if rank == 0 else None   # median / min of event-bracketed steps, beside the mean
-    total = aggregate_time(local, world)
-    t_step = total / steps
     n_kept = n_kept_of(kind, S, ratio)
     assert tuple(out[0].shape) == (B, H_KV, n_kept, D), out[0].shape
+    if dump_dir:
+        dump_outputs(dump_dir, out, world, rank)
+    ev_stats = event_timed_steps(step) if (full and rank == 0) else None   # median / min of event-bracketed steps, beside the mean
+    total = aggregate_time(local, world)
+    t_step = total / steps
 
     # ---- per-kernel HIP-event timing (profiling on: separate from the timed region) -------------
     roofline, kern_table = None, {}
-    if rank == 0:
+    if full and rank == 0:
         _native.prof_enable(True)
         nprof = 5
         for _ in range(nprof):
@@ -965,11 +1007,11 @@ def measure(workload, steps, warmup, prewarm_ms, world, rank, lo, hi, device, li
                            "kernels_avg_us_rocprofv3": {k: v[0] for k, v in (traced or {}).items() if not k.startswith("__")}}, f, indent=1)
 
     par = None
-    if parity and rank == 0:
+    if full and parity and rank == 0:
         with torch.no_grad():
             par = fixture_parity(workload, press, att, hidden, keys, values, kwargs, n_kept)
     # ---- CPU baseline (rank 0, N=1 only): the reference's op sequence in plain PyTorch on this box's host cores -------------
-    cpu_res = cpu_baseline(workload, press, att, rot, hidden, keys, values, kwargs, n_kept) if cpu else None
+    cpu_res = cpu_baseline(workload, press, att, rot, hidden, keys, values, kwargs, n_kept) if (full and cpu) else None
     res = {"t_step": t_step, "B": B, "n_kept": n_kept, "roofline": roofline, "cpu": cpu_res, "parity": par, "inputs": inputs_note,
            "kept_order": getattr(press, "kept_order", "position"), "step_events": ev_stats}
     del keys, values, hidden, out

@@ -12,7 +12,8 @@ def _pipe(device="cpu", dtype=None):
 
     import kvpress_amd  # noqa: F401  (registers the task)
 
-    return pipeline("kv-press-text-generation", model=_inputs.make_tiny_llama(dtype=dtype, device=device), tokenizer=_inputs.make_tiny_tokenizer())
+    return pipeline("kv-press-text-generation", model=_inputs.make_tiny_llama(dtype=dtype, device=device), tokenizer=_inputs.make_tiny_tokenizer(),
+                    device=device)
 
 
 def _sizes(cache):

@@ -184,6 +184,17 @@ def test_bench_refuses_a_rank_count_mismatch():
     assert r.returncode != 0 and "one rank per GPU" in r.stderr
 
 
+def test_bench_refuses_options_a_plain_run_would_ignore():
+    """--steps sets the number of timed steps (at least one); the per-kernel table and the trace statistics exist in --full runs only."""
+    import subprocess
+
+    for extra, why in ((["--steps", "0"], "--steps must be at least 1"), (["--profile-json", "x.json"], "need --full"),
+                       (["--trace-stats-csv", "x.csv"], "need --full")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub-step", "1", *extra], capture_output=True, text=True,
+                           timeout=120, cwd=ROOT)
+        assert r.returncode != 0 and why in r.stderr, (extra, r.stderr[-500:])
+
+
 def test_rank_failure_aborts_the_job():
     """VERDICT r4 #8b: a rank that raises inside the timed region (stub: rank 1 raises after the warm-up) must end the job with a
     non-zero exit instead of leaving rank 0 at the barrier -- through the self-launcher and under an external torchrun."""

@@ -571,7 +571,7 @@ def test_bench_measures_its_traffic_live():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "KVP_BENCH_CHILD")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "knorm32k", "--steps", "20", "--warmup", "5", "--prewarm-ms", "5",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     roof = line["roofline"]
@@ -595,7 +595,7 @@ def test_bench_two_ranks_real_kernels_on_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--workload", "knorm32k", "--steps", "5",
-                        "--warmup", "2", "--prewarm-ms", "5", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+                        "--warmup", "2", "--prewarm-ms", "5", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-1000:]
@@ -629,3 +629,42 @@ def test_bench_two_ranks_rccl():
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["steps"] == 3 and line["scaling"] == "weak" and line["config"]["batch_per_gpu"] == 1
     assert abs(line["value"] - 2 * 32768 / (32 * line["ms_per_step"] * 1e-3)) / line["value"] < 1e-3
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_the_last_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps and prints the headline fields only; --dump-outputs writes K', V'
+    of the last timed step as float32 .npy (Knorm 32k: 16384 kept rows per head are more than the byte budget, so a seeded sample of
+    rows) and they equal the same press run in this process on bench.py's seeded tensors."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import bench
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "KVP_BENCH_CHILD")}
+    out_dir = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "knorm32k", "--steps", "7", "--warmup", "2", "--prewarm-ms", "5",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-1000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["unit"] == "tok/s" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+    assert abs(line["value"] - 32768 / (32 * line["ms_per_step"] * 1e-3)) / line["value"] < 1e-3
+    assert line["roofline"] is None and line["cpu_baseline"] is None and not {"parity", "step_events", "extra"} & set(line)
+    assert sorted(os.listdir(out_dir)) == ["keys.npy", "values.npy"]
+    assert sum(os.path.getsize(out_dir / f) for f in os.listdir(out_dir)) <= 64e6
+    kind, S, ratio = bench.WORKLOADS["knorm32k"]
+    keys, values, hidden, _ = bench.bench_inputs("knorm32k", 0, DEV)
+    att, rot = llama_module()
+    with torch.no_grad():
+        pe = rot(hidden, torch.arange(S, device=DEV)[None])
+        ko, vo = bench.make_press(kind, ratio).compress(att, hidden, keys, values, None, {"position_embeddings": pe})
+    n = ko.shape[2]
+    for name, want in (("keys", ko), ("values", vo)):
+        got = np.load(out_dir / f"{name}.npy")
+        assert got.dtype == np.float32 and got.ndim == 4 and got.shape[:2] == (1, H_KV) and got.shape[3] == D and got.shape[2] < n
+        rows = np.sort(np.random.default_rng(0).choice(n, size=got.shape[2], replace=False))
+        assert np.array_equal(got, want[:, :, torch.from_numpy(rows).to(DEV)].float().cpu().numpy()), name

@@ -139,31 +139,34 @@ TORCH_PATH_CASES = [n for n in ALL if _inputs.spec(n)["kind"] in ("knorm", "snap
                     and _inputs.spec(n)["use_covariance"] and _inputs.spec(n)["use_vnorm"] and _inputs.spec(n)["epsilon"] == 0.0]
 
 
-@pytest.mark.parametrize("name", TORCH_PATH_CASES)
-def test_torch_path_is_the_reference_op_for_op(name):
-    """oracle/torch_path.py run on the seeded inputs reproduces the REAL reference's scores bit for bit, in float32 mode and
-    in the case's native dtype (same torch ops in the same order on the same CPU backend)."""
-    import torch
+@pytest.fixture(scope="module")
+def torch_path_pinned(tmp_path_factory):
+    """oracle/torch_path.py over TORCH_PATH_CASES in a fresh process on the pinned CPU backend (oracle/torch_path_pinned.py)"""
+    import subprocess
+    import sys
 
-    from oracle import torch_path as TP
+    from oracle import torch_path_pinned as TPP
+
+    out = str(tmp_path_factory.mktemp("torch_path") / "pinned.npz")
+    r = subprocess.run([sys.executable, TPP.__file__, out, *TORCH_PATH_CASES], env={**os.environ, **TPP.PINNED_ENV}, capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return np.load(out)
+
+
+@pytest.mark.parametrize("name", TORCH_PATH_CASES)
+def test_torch_path_is_the_reference_op_for_op(name, torch_path_pinned):
+    """oracle/torch_path.py run on the seeded inputs reproduces the REAL reference's scores bit for bit, in float32 mode and
+    in the case's native dtype (same torch ops in the same order on the same CPU backend: both run on the pinned backend of
+    oracle/torch_path_pinned.py; tests/golden/torch_path_pinned.json holds the digests of the reference's side: equal digests of dtype,
+    shape and bytes are equal bits)."""
+    import json
+
+    from oracle.torch_path_pinned import key, record
 
     s = _inputs.make_case(name)
-    g = load(name)
-    for mode, dt in (("f32", torch.float32), ("nat", _inputs.torch_dtype(s["dtype"]))):
-        att, rot, hidden, pe = _inputs.build_llama_attention(s, dt)
-        keys, values = torch.from_numpy(s["keys"]).to(dt), torch.from_numpy(s["values"]).to(dt)
-        kw = {"position_embeddings": pe}
-        with torch.no_grad():
-            if s["kind"] == "knorm":
-                sc = TP.knorm_score(att, hidden, keys, values, kw)
-            elif s["kind"] == "snapkv":
-                sc = TP.snapkv_score(att, hidden, keys, values, kw, W=s["W"], ks=s["ks"])
-            else:
-                sc = TP.ea_score(att, hidden, keys, values, kw, n_future=s["n_future"], n_sink=s["n_sink"])
-        ref = torch.from_numpy(g[f"scores_{mode}"])
-        assert torch.equal(sc.float(), ref), f"{name}/{mode}: max diff {(sc.float() - ref).abs().max()}"
-        if mode == "f32":
-            for i, r in enumerate(s["ratios"]):
-                ko, vo, idx = TP.torch_compress(lambda *a: sc, r, att, hidden, keys, values, kw)
-                assert ko.shape[2] == int(g[f"nkept_{i}"])
-                assert np.array_equal(np.sort(idx.numpy(), -1), g[f"idx_f32_{i}"])
+    g = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "torch_path_pinned.json")))
+    fields = ["scores_f32", "scores_nat"] + [f"{f}_{i}" for i in range(len(s["ratios"])) for f in ("nkept", "idx_f32")]
+    got = record({key(name, f): torch_path_pinned[key(name, f)] for f in fields})
+    for k, v in got.items():
+        assert v == g[k], f"{k}: restatement {v} != reference {g[k]}"

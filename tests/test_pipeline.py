@@ -25,7 +25,7 @@ def _run(name, device="cpu", dtype=None):
 
     spec, n_words, questions, max_new = _inputs.PIPELINE_CASES[name]
     model = _inputs.make_tiny_llama(dtype=dtype, device=device)
-    pipe = pipeline("kv-press-text-generation", model=model, tokenizer=_inputs.make_tiny_tokenizer())
+    pipe = pipeline("kv-press-text-generation", model=model, tokenizer=_inputs.make_tiny_tokenizer(), device=model.device)
     cache = _inputs.make_pipeline_cache(name, model.config)
     res = pipe(_inputs.tiny_context(n_words), questions=questions, press=_inputs.build_press(kvpress_amd, spec), max_new_tokens=max_new,
                cache=cache)
@@ -45,7 +45,7 @@ def _run_finch(name, device="cpu", dtype=None):
     import kvpress_amd
 
     cache = DynamicCache()
-    res, press = _inputs.run_finch_pipeline(kvpress_amd, lambda m, t: pipeline("kv-press-text-generation", model=m, tokenizer=t), name, cache,
+    res, press = _inputs.run_finch_pipeline(kvpress_amd, lambda m, t: pipeline("kv-press-text-generation", model=m, tokenizer=t, device=m.device), name, cache,
                                             dtype=dtype, device=device)
     assert press.window_size == GOLD[name]["window_size"]
     assert [int(cache.get_seq_length(i)) for i in range(len(cache))] == GOLD[name]["cache_lengths"]
@@ -63,7 +63,8 @@ def _run_family(name, device="cpu", dtype=None):
     import kvpress_amd
 
     family, spec, n_words, questions, max_new = _inputs.FAMILY_PIPELINE_CASES[name]
-    pipe = pipeline("kv-press-text-generation", model=_inputs.make_tiny_model(family, dtype=dtype, device=device), tokenizer=_inputs.make_tiny_tokenizer())
+    pipe = pipeline("kv-press-text-generation", model=_inputs.make_tiny_model(family, dtype=dtype, device=device), tokenizer=_inputs.make_tiny_tokenizer(),
+                    device=device)
     cache = DynamicCache()
     res = pipe(_inputs.tiny_context(n_words), questions=questions, press=_inputs.build_press(kvpress_amd, spec), max_new_tokens=max_new, cache=cache)
     assert [int(cache.get_seq_length(i)) for i in range(len(cache))] == GOLD[name]["cache_lengths"]
@@ -82,7 +83,7 @@ def test_single_question_and_registry(fake_native):
     import kvpress_amd as P
     from kvpress_amd.pipeline import KVPressTextGenerationPipeline
 
-    pipe = pipeline("kv-press-text-generation", model=_inputs.make_tiny_llama(), tokenizer=_inputs.make_tiny_tokenizer())
+    pipe = pipeline("kv-press-text-generation", model=_inputs.make_tiny_llama(), tokenizer=_inputs.make_tiny_tokenizer(), device="cpu")
     assert isinstance(pipe, KVPressTextGenerationPipeline)
     spec, n_words, questions, max_new = _inputs.PIPELINE_CASES["pipe_knorm"]
     out = pipe(_inputs.tiny_context(n_words), question=questions[0], press=_inputs.build_press(P, spec), max_new_tokens=max_new)
@@ -96,7 +97,7 @@ def test_decoding_press_rejects_multiple_questions(fake_native):
 
     import kvpress_amd as P
 
-    pipe = pipeline("kv-press-text-generation", model=_inputs.make_tiny_llama(), tokenizer=_inputs.make_tiny_tokenizer())
+    pipe = pipeline("kv-press-text-generation", model=_inputs.make_tiny_llama(), tokenizer=_inputs.make_tiny_tokenizer(), device="cpu")
     with pytest.raises(ValueError):
         pipe("w1 w2 w3", questions=["w1", "w2"], press=P.DecodingPress(P.KnormPress(), 2, 8, 0), max_new_tokens=2)
 
@@ -137,7 +138,7 @@ def test_context_truncation(fake_native):
 
     import kvpress_amd.pipeline  # noqa: F401
 
-    pipe = pipeline("kv-press-text-generation", model=_inputs.make_tiny_llama(), tokenizer=_inputs.make_tiny_tokenizer())
+    pipe = pipeline("kv-press-text-generation", model=_inputs.make_tiny_llama(), tokenizer=_inputs.make_tiny_tokenizer(), device="cpu")
     cache = DynamicCache()
     pipe(_inputs.tiny_context(100), question="w1", max_new_tokens=2, max_context_length=30, cache=cache)
     assert cache.get_seq_length() == 30

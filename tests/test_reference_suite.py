@@ -170,7 +170,7 @@ def test_pipeline_logs_and_variants(fake_native, caplog):
 
     import kvpress_amd as P
 
-    pipe = pipeline("kv-press-text-generation", model=_inputs.make_tiny_llama(), tokenizer=_inputs.make_tiny_tokenizer())
+    pipe = pipeline("kv-press-text-generation", model=_inputs.make_tiny_llama(), tokenizer=_inputs.make_tiny_tokenizer(), device="cpu")
     context = _inputs.tiny_context(22)   # 23 tokens with bos, like the reference's test sentence
     # (the reference also asks the empty question, which its tokenizer turns into the "\n" suffix token; the in-memory word
     # tokenizer has no such token, so that variant would feed zero tokens)
@@ -192,7 +192,7 @@ def test_pipeline_context_cache_is_invariant(fake_native):
     from kvpress_amd.pipeline import KVPressTextGenerationPipeline
 
     model, tok = _inputs.make_tiny_llama(), _inputs.make_tiny_tokenizer()
-    pipe = KVPressTextGenerationPipeline(model=model, tokenizer=tok)
+    pipe = KVPressTextGenerationPipeline(model=model, tokenizer=tok, device=model.device)
     q_ids = tok("w1 w2 w3", return_tensors="pt", add_special_tokens=False)["input_ids"]
     with torch.no_grad():
         cache = DynamicCache()
