@@ -37,7 +37,8 @@ extern "C" {
 typedef void* kvp_stream_t; /* hipStream_t */
 
 enum kvp_dtype { KVP_F32 = 0, KVP_F16 = 1, KVP_BF16 = 2 };
-enum kvp_status { KVP_OK = 0, KVP_EINVAL = -1, KVP_EUNSUPPORTED = -2, KVP_EWORKSPACE = -3, KVP_EHIP = -4, KVP_EASYNC = -5 };
+enum kvp_status { KVP_OK = 0, KVP_EINVAL = -1, KVP_EUNSUPPORTED = -2, KVP_EWORKSPACE = -3, KVP_EHIP = -4, KVP_EASYNC = -5,
+                  KVP_ENUMERIC = -6 /* kvp_leverage_status: the Cholesky factorisation failed */ };
 /* Order of the retained indices.  POSITION: ascending token position (default; makes the gather a
  * monotone stream).  SCORE: descending score, ties by ascending position -- the element order
  * torch.topk(sorted=True) produces at scorer_press.py:95, for tensor-exact comparisons. */
@@ -257,6 +258,44 @@ int kvp_snapkv_compress_hidden(const void* hidden_win, int64_t x_sb, int64_t x_s
                                int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int64_t D, int kernel_size,
                                int64_t n_kept, void* k_out, void* v_out, void* ws, size_t ws_bytes, int flags,
                                kvp_stream_t stream);
+
+/* ---- NonCausalAttnPress.score (kvpress/presses/non_causal_attention_press.py:47-122) --------------------------------------------
+ * q: PRE-RoPE queries [B,Hq,S,D]; cos/sin: the rotary tables of the same S positions [Bc,S,D] (cs_sb = 0 broadcasts), RoPE'd in the
+ * library with torch's per-op rounding (:114); k: post-RoPE keys, v: values [B,Hkv,S,D], all in `dtype`, strides in elements.
+ * Per chunk of `chunk` tokens (the last one zero-padded; padded keys get logit -1e-9 from every row, padded queries 0: :70-88):
+ * logits = q k^T (NOT scaled, rounded to the dtype like the matmul output), float32 row softmax, sum over the chunk's queries (:89-93),
+ * mean over the Hq/Hkv group (:118), times ||v|| (:120), avg_pool1d(3, pad 1) (:121), then the z-score over the WHOLE [B,Hkv,S] tensor
+ * (mean, unbiased std clamped at 1e-6: :122).  raw (may be NULL): the scores before the z-score; scores: the z-scores; both
+ * contiguous [B,Hkv,S] float32.  bf16 / f16 with D in {64,96,128,256}, chunk % 32 == 0, chunk <= 512, Hq/Hkv <= 16 and 16-byte aligned
+ * key rows run on the matrix cores; everything else (float32, other shapes) on a generic kernel.  S >= 1;
+ * B*Hkv*S = 1 gives a NaN z-score, as torch's std of one element does. */
+size_t kvp_ncattn_workspace_bytes(int64_t B, int64_t Hkv, int64_t S);
+int kvp_ncattn_score(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const void* cos, const void* sin, int64_t cs_sb,
+                     int64_t cs_ss, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* v, int64_t v_sb,
+                     int64_t v_sh, int64_t v_ss, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t D,
+                     int64_t chunk, float* raw, float* scores, void* ws, size_t ws_bytes, kvp_stream_t stream);
+
+/* ---- LeverageScorePress.compute_leverage_scores + score (kvpress/presses/leverage_press.py:47-110) ---------------------------------
+ * k: PRE-RoPE keys [B,H,S,D] (D <= 256); phi: the Gaussian sketch [B,H,D,sketch] the caller drew (:68-75; last dim contiguous, strides
+ * p_sb, p_sh, p_sd in elements), same dtype as k.  x_s = phi^T (k_s - mean_s k) rounded to the dtype (:78-79), G = sum_s x_s x_s^T
+ * symmetrised, L = cholesky(G + jitter I) with jitter 1e-2, x10, at most 5 tries (:47-56, :90; float64), raw_s = max(0, ||L^-1 x_s||^2)
+ * (:95-109), then the global z-score of :110 (NaN for B*H*S = 1, as torch's std).  raw may be NULL.  1 <= sketch <= 256. */
+size_t kvp_leverage_workspace_bytes(int64_t B, int64_t H, int64_t S, int64_t D, int64_t sketch);
+int kvp_leverage_score(const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* phi, int64_t p_sb, int64_t p_sh,
+                       int64_t p_sd, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, int64_t sketch, float* raw,
+                       float* scores, void* ws, size_t ws_bytes, kvp_stream_t stream);
+/* The failure of leverage_press.py:56 (`raise RuntimeError("Cholesky failed after 5 tries")`): reads the per-head status the last
+ * kvp_leverage_score on workspace `ws` (same shape arguments) left, SYNCHRONISING `stream` -- as the reference's check of `info` does
+ * at :53 -- and returns KVP_ENUMERIC with that message if a head failed (its scores are NaN), else KVP_OK. */
+int kvp_leverage_status(const void* ws, int64_t B, int64_t H, int64_t S, int64_t D, int64_t sketch, kvp_stream_t stream);
+
+/* ---- CompactorPress.score tail (kvpress/presses/compactor_press.py:114-122) -------------------------------------------------------
+ * scores[b,h,sink_start + s] = blending * z_lev[b,h,s] + z_attn[b,h,s] for s < S_inner (z_* contiguous [B,H,S_inner] float32); the
+ * first sink_start and last sink_end positions of each row of scores (contiguous [B,H,S_inner+sink_start+sink_end]) get the global
+ * max of the blended scores (F.pad(..., value=scores.max()), :121; NaN if any blended score is NaN, as torch's max). */
+size_t kvp_compactor_combine_workspace_bytes(void);
+int kvp_compactor_combine(const float* z_lev, const float* z_attn, int64_t B, int64_t H, int64_t S_inner, int64_t sink_start,
+                          int64_t sink_end, float blending, float* scores, void* ws, size_t ws_bytes, kvp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,15 @@ SIGNATURES = {
                               c_void_p, _I64, c_void_p, c_void_p, c_void_p]),
     "kvp_gather_kv_rerotate": (c_int, [c_void_p, _I64, _I64, _I64, c_void_p, _I64, _I64, _I64, c_int, _I64, _I64, _I64, _I64,
                                        c_void_p, _I64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "kvp_ncattn_workspace_bytes": (c_size_t, [_I64] * 3),
+    "kvp_ncattn_score": (c_int, [c_void_p, _I64, _I64, _I64, c_void_p, c_void_p, _I64, _I64, c_void_p, _I64, _I64, _I64, c_void_p, _I64, _I64,
+                                 _I64, c_int, _I64, _I64, _I64, _I64, _I64, _I64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "kvp_leverage_workspace_bytes": (c_size_t, [_I64] * 5),
+    "kvp_leverage_score": (c_int, [c_void_p, _I64, _I64, _I64, c_void_p, _I64, _I64, _I64, c_int, _I64, _I64, _I64, _I64, _I64,
+                                   c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "kvp_leverage_status": (c_int, [c_void_p, _I64, _I64, _I64, _I64, _I64, c_void_p]),
+    "kvp_compactor_combine_workspace_bytes": (c_size_t, []),
+    "kvp_compactor_combine": (c_int, [c_void_p, c_void_p, _I64, _I64, _I64, _I64, _I64, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 # include/kvpress_hip_lab.h: measurement / test aids of the same library (bench.py, tools/, the select's residency tests)
 LAB_SIGNATURES = {
@@ -871,3 +880,73 @@ def prof_records():
 def tuning_reload() -> None:
     """Make the library re-read its KVP_* tuning variables (they are read from the environment once and cached)."""
     _check(lib().kvp_tuning_reload(), "kvp_tuning_reload")
+
+
+# ---- the Compactor family (non_causal_attention_press.py, leverage_press.py, compactor_press.py) --------------------------------------
+def ncattn_score(q_pre: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, keys: torch.Tensor, values: torch.Tensor, chunk_size: int,
+                 return_raw: bool = False):
+    """NonCausalAttnPress scores (non_causal_attention_press.py:95-122): z-scores [B,Hkv,S] float32 from the PRE-RoPE queries
+    [B,Hq,S,D], the rotary tables of the same S positions [1 or B, S, D], keys and values [B,Hkv,S,D]; with ``return_raw`` also the
+    scores before the z-score."""
+    keys = _rows_last_contig(_dev(keys))
+    values = _rows_last_contig(_dev(values))
+    q_pre = _rows_last_contig(_dev(q_pre))
+    dt = keys.dtype
+    if q_pre.dtype != dt:
+        q_pre = q_pre.to(dt)
+    if values.dtype != dt:
+        values = values.to(dt)
+    B, Hq, S, D = q_pre.shape
+    Bk, Hkv, Sk, Dk = keys.shape
+    assert B == Bk and S == Sk and D == Dk and tuple(values.shape[:3]) == (B, Hkv, S) and values.shape[3] == D, (q_pre.shape, keys.shape, values.shape)
+    if Hq % Hkv != 0:
+        raise KvpressHipError(f"kvp_ncattn_score: Hq % Hkv != 0 ({Hq}, {Hkv})")
+    cos = _rows_last_contig(_dev(cos.to(dt)))
+    sin = _rows_last_contig(_dev(sin.to(dt)))
+    assert cos.shape == sin.shape and cos.shape[-1] == D and cos.shape[-2] == S and cos.shape[0] in (1, B), (cos.shape, q_pre.shape)
+    if sin.stride() != cos.stride():
+        cos, sin = cos.contiguous(), sin.contiguous()
+    raw = torch.empty((B, Hkv, S), dtype=torch.float32, device=keys.device) if return_raw else None
+    z = torch.empty((B, Hkv, S), dtype=torch.float32, device=keys.device)
+    with _on_device(keys.device):
+        ws = _ws(lib().kvp_ncattn_workspace_bytes(B, Hkv, S), keys)
+        _check(lib().kvp_ncattn_score(_p(q_pre), _st(q_pre, 0), _st(q_pre, 1), _st(q_pre, 2), _p(cos), _p(sin), _st(cos, 0), _st(cos, 1),
+                                      _p(keys), _st(keys, 0), _st(keys, 1), _st(keys, 2), _p(values), _st(values, 0), _st(values, 1),
+                                      _st(values, 2), _DTYPES[dt], B, Hq, Hkv, S, D, int(chunk_size), _p(raw), _p(z), _p(ws), ws.numel(),
+                                      _stream(keys)), "kvp_ncattn_score")
+    return (z, raw) if return_raw else z
+
+
+def leverage_score(keys_pre: torch.Tensor, phi: torch.Tensor, return_raw: bool = False):
+    """LeverageScorePress scores (leverage_press.py:59-110): z-scores [B,H,S] float32 from the PRE-RoPE keys [B,H,S,D] and the
+    Gaussian sketch phi [B,H,D,k] (drawn by the caller, leverage_press.py:68-75).  Synchronises the stream to check the Cholesky
+    factorisation, as the reference does; raises KvpressHipError("... Cholesky failed after 5 tries ...") like its RuntimeError."""
+    k = _rows_last_contig(_dev(keys_pre))
+    phi = _rows_last_contig(_dev(phi))
+    if phi.dtype != k.dtype:
+        phi = phi.to(k.dtype)
+    B, H, S, D = k.shape
+    assert tuple(phi.shape[:3]) == (B, H, D), (phi.shape, k.shape)
+    ks = phi.shape[3]
+    raw = torch.empty((B, H, S), dtype=torch.float32, device=k.device) if return_raw else None
+    z = torch.empty((B, H, S), dtype=torch.float32, device=k.device)
+    with _on_device(k.device):
+        ws = _ws(lib().kvp_leverage_workspace_bytes(B, H, S, D, ks), k)
+        _check(lib().kvp_leverage_score(_p(k), _st(k, 0), _st(k, 1), _st(k, 2), _p(phi), _st(phi, 0), _st(phi, 1), _st(phi, 2),
+                                        _DTYPES[k.dtype], B, H, S, D, ks, _p(raw), _p(z), _p(ws), ws.numel(), _stream(k)), "kvp_leverage_score")
+        _check(lib().kvp_leverage_status(_p(ws), B, H, S, D, ks, _stream(k)), "kvp_leverage_score")
+    return (z, raw) if return_raw else z
+
+
+def compactor_combine(z_lev: torch.Tensor, z_attn: torch.Tensor, sink_start: int, sink_end: int, blending: float) -> torch.Tensor:
+    """blending * z_lev + z_attn, padded with sink_start / sink_end positions holding the global max (compactor_press.py:119-122)."""
+    z_lev = _dev(z_lev).contiguous()
+    z_attn = _dev(z_attn).contiguous()
+    assert z_lev.shape == z_attn.shape and z_lev.dtype == torch.float32 and z_attn.dtype == torch.float32, (z_lev.shape, z_attn.shape)
+    B, H, Si = z_lev.shape
+    out = torch.empty((B, H, Si + sink_start + sink_end), dtype=torch.float32, device=z_lev.device)
+    with _on_device(z_lev.device):
+        ws = _ws(lib().kvp_compactor_combine_workspace_bytes(), z_lev)
+        _check(lib().kvp_compactor_combine(_p(z_lev), _p(z_attn), B, H, Si, int(sink_start), int(sink_end), float(blending), _p(out), _p(ws),
+                                           ws.numel(), _stream(z_lev)), "kvp_compactor_combine")
+    return out

@@ -1,6 +1,6 @@
 """Host-side helpers of the hot path: the query projection and cache access.
 
-Mirrors kvpress/utils.py of the reference (get_prerope_query_states :12-53,
+Mirrors kvpress/utils.py of the reference (get_prerope_query_states :12-53, get_prerope_key_states :56-95,
 extract_keys_and_values :104-114).  These call model-owned modules (``q_proj`` may be
 quantised / LoRA-wrapped) and therefore stay PyTorch calls on the model's device.
 """
@@ -33,6 +33,28 @@ def get_prerope_query_states(module: nn.Module, hidden_states: torch.Tensor) -> 
     if _is_instance_named(module, "Qwen3Attention", "Gemma3Attention"):
         query_states = module.q_norm(query_states)
     return query_states
+
+
+def get_prerope_key_states(module: nn.Module, hidden_states: torch.Tensor) -> torch.Tensor:
+    """Key states before RoPE, [B, num_key_value_heads, k_len, head_dim] (reference utils.py:56-95).
+
+    Phi3 fuses q/k/v in ``qkv_proj`` (keys follow the num_heads*head_dim query features); Llama-like layers have ``k_proj``;
+    Qwen3 / Gemma3 apply ``k_norm`` per head.  The projection is the model's own module (a torch call).
+    """
+    bsz, k_len, _ = hidden_states.shape
+    head_dim = module.head_dim
+    if _is_instance_named(module, "Phi3Attention"):
+        qkv = module.qkv_proj(hidden_states)
+        query_pos = module.config.num_attention_heads * module.head_dim
+        key_states = qkv[..., query_pos: query_pos + module.num_key_value_heads * module.head_dim]
+    elif hasattr(module, "k_proj"):
+        key_states = module.k_proj(hidden_states)
+    else:
+        raise NotImplementedError(f"Press not yet implemented for {module.__class__}.")
+    key_states = key_states.view(bsz, k_len, -1, head_dim).transpose(1, 2)
+    if _is_instance_named(module, "Qwen3Attention", "Gemma3Attention"):
+        key_states = module.k_norm(key_states)
+    return key_states
 
 
 def _is_quantized(cache) -> bool:
