@@ -297,6 +297,27 @@ size_t kvp_compactor_combine_workspace_bytes(void);
 int kvp_compactor_combine(const float* z_lev, const float* z_attn, int64_t B, int64_t H, int64_t S_inner, int64_t sink_start,
                           int64_t sink_end, float blending, float* scores, void* ws, size_t ws_bytes, kvp_stream_t stream);
 
+/* ---- MergingPress.merge (kvpress/presses/merging_press.py:99-177) -------------------------------------------------------------------
+ * After kvp_topk_select + kvp_gather_kv: every evicted token's value is folded into the value of its most cosine-similar kept token,
+ * IN PLACE in the gathered V' (v_out).  k / v: the cache's keys and values [B,H,S,D] (element strides); kept_idx: int32 [B,H,n_kept] in
+ * the order the select wrote them (either kvp_order); k_out (read only) / v_out: the contiguous gathered K' / V' [B,H,n_kept,D].  The
+ * evicted tokens are the complement of the kept set in ascending position (:124-127).  target = argmax_j cos(k_e, k'_j) over the kept
+ * list (ties: the LOWEST index in it, torch's first occurrence), max_sim its cosine (:137-139); the gates (:141-150): max_sim >=
+ * similarity_threshold (compared in float32) and, for merge_fraction < 1, max_sim >= the per-row torch.quantile(1 - merge_fraction) of
+ * max_sim with failed entries at -inf, with ATen's float32 rank and lerp (a NaN quantile, which torch returns when the lower order
+ * statistic is -inf and the lerp weight is below 0.5, lets nothing in that row merge); w = clamp(max_sim, 0) * gate * |v_e| / (|v_e| +
+ * |v'_t| + 1e-6) with |v'_t| from V' before the merge (:152-156); rows with sum(w) > 0 become ((v' + sum w v_e) / (1 + sum w)) rounded
+ * to the dtype, the sums in float32 in ascending evicted position, the others are left untouched (:158-173).  target (int32) and
+ * max_sim (float32), [B,H,S - n_kept] contiguous, may be NULL.  Nothing happens when n_kept == 0 or n_kept == S (:120-121).  D <= 256;
+ * bf16 / f16 with D in {64,96,128,256} and 16-byte aligned key rows run the similarity GEMM on the matrix cores, everything else on a
+ * generic kernel.  Workspace: 32 bytes per (b, h, token) + O(B*H*S / 1024); never anything of size n_evict x n_kept.  Bit-identical
+ * results from run to run (no float atomics). */
+size_t kvp_merge_workspace_bytes(int64_t B, int64_t H, int64_t S, int64_t n_kept, int64_t D);
+int kvp_merge_values(const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* v, int64_t v_sb, int64_t v_sh, int64_t v_ss,
+                     const int32_t* kept_idx, const void* k_out, void* v_out, int dtype, int64_t B, int64_t H, int64_t S, int64_t n_kept,
+                     int64_t D, double similarity_threshold, double merge_fraction, void* ws, size_t ws_bytes, int32_t* target,
+                     float* max_sim, kvp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

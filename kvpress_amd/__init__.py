@@ -19,6 +19,7 @@ from kvpress_amd.presses.key_rerotation_press import KeyRerotationPress
 from kvpress_amd.presses.keydiff_press import KeyDiffPress
 from kvpress_amd.presses.knorm_press import KnormPress
 from kvpress_amd.presses.leverage_press import LeverageScorePress
+from kvpress_amd.presses.merging_press import MergingPress
 from kvpress_amd.presses.non_causal_attention_press import NonCausalAttnPress
 from kvpress_amd.presses.per_layer_compression_press import PerLayerCompressionPress
 from kvpress_amd.presses.pyramidkv_press import PyramidKVPress
@@ -32,11 +33,11 @@ from kvpress_amd.presses.tova_press import TOVAPress
 __version__ = "0.1.0"
 # the path (a), the scorers that reuse its kernels (f-2), the selection wrappers (f-3), the decode-time step (f-4), the
 # pipeline (f-1); plus four tiny host-only presses the reference's own test fixtures for those rows are built from (Composed, PerLayer,
-# Random, StreamingLLM); plus the Compactor family (NonCausalAttn, LeverageScore, Compactor: DESIGN.md section 9).  Presses outside that scope that still have kernels here live in kvpress_amd.contrib.
+# Random, StreamingLLM); plus the Compactor family (NonCausalAttn, LeverageScore, Compactor) and MergingPress.  Presses outside that scope that still have kernels here live in kvpress_amd.contrib.
 __all__ = ["BasePress", "ScorerPress", "KnormPress", "SnapKVPress", "ExpectedAttentionPress", "PyramidKVPress", "TOVAPress", "KeyDiffPress", "QFilterPress",
            "CURPress", "FinchPress", "ChunkPress", "KeyRerotationPress", "AdaKVPress", "DecodingPress", "CompressionRatioDecodingPress", "PrefillDecodingPress",
            "ComposedPress", "PerLayerCompressionPress", "RandomPress", "StreamingLLMPress", "KVPressTextGenerationPipeline",
-           "NonCausalAttnPress", "LeverageScorePress", "CompactorPress"]
+           "NonCausalAttnPress", "LeverageScorePress", "CompactorPress", "MergingPress"]
 
 
 # The reference exports every press at top level (kvpress/__init__.py:7-49).  The five out-of-scope presses that exist here resolve
@@ -45,7 +46,7 @@ __all__ = ["BasePress", "ScorerPress", "KnormPress", "SnapKVPress", "ExpectedAtt
 _CONTRIB = ("BlockPress", "ChunkKVPress", "LagKVPress", "ObservedAttentionPress", "ThinKPress")
 _NOT_BUILT = ("CAMPress", "CapPress", "CriticalAdaKVPress", "CriticalKVPress", "DMSPress", "DuoAttentionPress",
               "ExpectedAttentionStatsPress", "FastKVzipPress", "KVComposePress", "KVzapPress", "KVzipPress", "LUKVPress",
-              "MergingPress", "RestoreKVPress", "SimLayerKVPress")
+              "RestoreKVPress", "SimLayerKVPress")
 
 
 def __getattr__(name):

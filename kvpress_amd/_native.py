@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 from typing import Optional
 
 import torch  # must be imported before the .so so that it binds to torch's libamdhip64.so.7
@@ -89,6 +89,9 @@ SIGNATURES = {
     "kvp_leverage_status": (c_int, [c_void_p, _I64, _I64, _I64, _I64, _I64, c_void_p]),
     "kvp_compactor_combine_workspace_bytes": (c_size_t, []),
     "kvp_compactor_combine": (c_int, [c_void_p, c_void_p, _I64, _I64, _I64, _I64, _I64, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "kvp_merge_workspace_bytes": (c_size_t, [_I64] * 5),
+    "kvp_merge_values": (c_int, [c_void_p, _I64, _I64, _I64, c_void_p, _I64, _I64, _I64, c_void_p, c_void_p, c_void_p, c_int, _I64, _I64, _I64,
+                                 _I64, _I64, c_double, c_double, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
 }
 # include/kvpress_hip_lab.h: measurement / test aids of the same library (bench.py, tools/, the select's residency tests)
 LAB_SIGNATURES = {
@@ -950,3 +953,31 @@ def compactor_combine(z_lev: torch.Tensor, z_attn: torch.Tensor, sink_start: int
         _check(lib().kvp_compactor_combine(_p(z_lev), _p(z_attn), B, H, Si, int(sink_start), int(sink_end), float(blending), _p(out), _p(ws),
                                            ws.numel(), _stream(z_lev)), "kvp_compactor_combine")
     return out
+
+
+# ---- MergingPress (merging_press.py:99-177) ---------------------------------------------------------------------------------------------
+def merge_values_(keys: torch.Tensor, values: torch.Tensor, kept_idx: torch.Tensor, k_out: torch.Tensor, v_out: torch.Tensor,
+                  threshold: float, fraction: float, target: Optional[torch.Tensor] = None, max_sim: Optional[torch.Tensor] = None):
+    """MergingPress.merge after the select and the gather: folds every evicted token's value (keys / values [B,H,S,D], evicted = not in
+    the int32 kept_idx [B,H,n_kept]) into its most cosine-similar kept row, IN PLACE in v_out (the contiguous gathered V'; k_out is the
+    gathered K').  ``target`` (int32) / ``max_sim`` (float32) [B,H,S-n_kept], if given, receive the argmax and its cosine.  Returns v_out."""
+    keys = _rows_last_contig(_dev(keys))
+    values = _rows_last_contig(_dev(values))
+    dt = keys.dtype
+    B, H, S, D = keys.shape
+    assert values.dtype == dt and tuple(values.shape) == (B, H, S, D), (keys.shape, values.shape)
+    n = kept_idx.shape[-1]
+    assert tuple(kept_idx.shape) == (B, H, n) and kept_idx.dtype == torch.int32 and kept_idx.is_contiguous(), (kept_idx.shape, kept_idx.dtype)
+    for t in (k_out, v_out):
+        assert t.dtype == dt and tuple(t.shape) == (B, H, n, D) and t.is_contiguous() and t.device == keys.device, (t.shape, t.dtype)
+    for t, tdt in ((target, torch.int32), (max_sim, torch.float32)):
+        if t is not None:
+            assert t.dtype == tdt and tuple(t.shape) == (B, H, S - n) and t.is_contiguous(), (t.shape, t.dtype)
+    if n == 0 or n == S:
+        return v_out
+    with _on_device(keys.device):
+        ws = _ws(lib().kvp_merge_workspace_bytes(B, H, S, n, D), keys)
+        _check(lib().kvp_merge_values(_p(keys), _st(keys, 0), _st(keys, 1), _st(keys, 2), _p(values), _st(values, 0), _st(values, 1),
+                                      _st(values, 2), _p(kept_idx), _p(k_out), _p(v_out), _DTYPES[dt], B, H, S, n, D, float(threshold),
+                                      float(fraction), _p(ws), ws.numel(), _p(target), _p(max_sim), _stream(keys)), "kvp_merge_values")
+    return v_out
