@@ -15,8 +15,11 @@
  *   - 4-D tensors are [B, H, S, D] views with the last dim contiguous; strides are in ELEMENTS
  *     (sb, sh, ss) so sliced cache views (keys[:, :, n_sink:], chunk slices) need no copy;
  *   - outputs and workspaces are caller-allocated; *_workspace_bytes() gives the size;
- *   - every call is asynchronous on `stream` (a hipStream_t), allocates nothing, never
- *     synchronises, keeps no global state and is thread-safe;
+ *   - every call is asynchronous on `stream` (a hipStream_t), allocates no device memory, never
+ *     synchronises (kvp_leverage_status excepted) and is thread-safe;
+ *   - process-wide state, created on first use and kept until exit: one host-pinned status word
+ *     (kvp_async_error_check below) and, per device, a stream guard that orders the one-launch
+ *     select of long rows ("one cluster select per device" at kvp_topk_select);
  *   - return 0 (KVP_OK) or a negative KVP_E* code; kvp_last_error() returns the calling
  *     thread's last message.
  *   - scores are always float32 (the reference returns the model dtype; float32 is a superset
@@ -146,7 +149,12 @@ int kvp_ea_score(const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss,
 /* ---- ScorerPress.compress: top-k + gather (kvpress/presses/scorer_press.py:94-100) ----------
  * kvp_topk_select: for each of the R rows of scores[R, S] (row stride in elements) write the
  * indices of the k largest scores to idx[R, k] (int32).  torch.topk leaves ties unspecified;
- * here the LOWEST POSITION wins among equal scores, and -0.0 == +0.0.  0 <= k <= S. */
+ * here the LOWEST POSITION wins among equal scores, and -0.0 == +0.0.  0 <= k <= S.
+ * One cluster select per device: rows of 16385 .. 262144 scores are selected by ONE launch whose workgroups wait for each other
+ * (kvp_async_error_check above), so only one such launch may be in flight on a device.  Within a process the library sees to that
+ * itself (the per-device stream guard makes a call on another stream wait for the previous one).  Processes that SHARE a GPU must
+ * set KVP_TK_CLUSTER=0 in their environment, which takes the multi-launch select instead; otherwise two of them can hold the CUs
+ * each other's rows wait for, and the bounded spin ends in KVP_EASYNC. */
 size_t kvp_topk_workspace_bytes(int64_t R, int64_t S, int64_t k);
 /* workspace for order == KVP_ORDER_SCORE (the select's + the sort's); KVP_ORDER_POSITION needs only the one above */
 size_t kvp_topk_order_workspace_bytes(int64_t R, int64_t S, int64_t k);
@@ -196,7 +204,9 @@ int kvp_gather_kv_rerotate(const void* k, int64_t k_sb, int64_t k_sh, int64_t k_
  * flags: KVP_TOPK_WS_CLEAN if the first kvp_topk_workspace_bytes(R, S, n_kept) bytes of ws were zero-filled once and
  * the workspace has only been used by these calls on ONE stream since (they leave it clean), else 0;
  * | KVP_ORDER_SCORE: the rows of k_out / v_out in descending score order, ties by ascending position (SnapKV: the window tokens
- * first) -- the order in which the reference stores them (scorer_press.py:95-100); default: ascending position. */
+ * first) -- the order in which the reference stores them (scorer_press.py:95-100); default: ascending position.
+ * kvp_knorm_compress and the two kvp_snapkv_compress_* entries run the one-launch select on long rows: "one cluster select per
+ * device" at kvp_topk_select holds for them too (KVP_TK_CLUSTER=0 when processes share a GPU). */
 size_t kvp_knorm_compress_workspace_bytes(int64_t B, int64_t H, int64_t S, int64_t n_kept);
 int kvp_knorm_compress(const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss,
                        const void* v, int64_t v_sb, int64_t v_sh, int64_t v_ss, int dtype,
@@ -242,7 +252,8 @@ int kvp_scores_head_mean(float* scores, int64_t B, int64_t H, int64_t S, int64_t
  * hidden % 256 == 0, else KVP_EUNSUPPORTED (the caller then runs its own q_proj and kvp_snapkv_*_rope).
  * kvp_snapkv_qproj_rope writes the RoPE'd window queries q_rot [B, Hq, W, D] (contiguous, input dtype): fp32 accumulation
  * in a fixed order, rounded to the dtype like a GEMM output, then rotated with torch's per-op rounding.
- * kvp_snapkv_score_hidden / kvp_snapkv_compress_hidden = kvp_snapkv_score_rope / kvp_snapkv_compress_rope from there. */
+ * kvp_snapkv_score_hidden / kvp_snapkv_compress_hidden = kvp_snapkv_score_rope / kvp_snapkv_compress_rope from there
+ * (kvp_snapkv_compress_hidden: one cluster select per device, as kvp_snapkv_compress_rope). */
 int kvp_snapkv_qproj_rope(const void* hidden_win, int64_t x_sb, int64_t x_sw, const void* wq, const void* cos, const void* sin,
                           int64_t cs_sb, int64_t cs_sw, int dtype, int64_t B, int64_t Hq, int64_t W, int64_t D, int64_t hidden,
                           void* q_rot, kvp_stream_t stream);

@@ -27,7 +27,8 @@ CONTRIB_LIB = os.path.join(LIBDIR, "libkvpress_hip_contrib.so")
 CONTRIB_SRC = os.path.join(CSRC, "contrib")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 ARCH = "gfx950"
-FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
+# hidden by default: the libraries export the extern "C" entries of include/*.h and csrc/kvp_host.h's KVP_INTERNAL_API, nothing else
+FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-fvisibility=hidden", "-fvisibility-inlines-hidden"]
 # MFMA results straight into VGPRs (gfx950 has a unified register file): the softmax epilogues read every
 # accumulator element with VALU ops, and v_accvgpr_read was 16 of their 73 instructions per 16 logits.
 FILE_FLAGS = {"snapkv_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "ea_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
@@ -65,6 +66,16 @@ def up_to_date() -> bool:
     return all(os.path.getmtime(p) <= t for p in sources() + contrib_sources() + _deps() + [os.path.abspath(__file__)])
 
 
+def _run(cmd, what: str, verbose: bool) -> None:
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"{what}:\n{r.stdout}\n{r.stderr}")
+    if verbose and r.stderr.strip():
+        print(r.stderr, file=sys.stderr)
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     if not force and up_to_date():
         return LIB
@@ -72,54 +83,28 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJDIR, exist_ok=True)
     hipcc = _hipcc()
     hdr_t = max(os.path.getmtime(p) for p in _deps())
+    link = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o"]
 
     def compile_one(src):
         obj = os.path.join(OBJDIR, ("contrib_" if os.path.dirname(src) == CONTRIB_SRC else "") + os.path.basename(src)[:-4] + ".o")
-        if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), hdr_t):
-            return obj
-        cmd = [hipcc, *flags_for(src), "-c", src, "-o", obj]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")
-        if verbose and r.stderr.strip():
-            print(r.stderr, file=sys.stderr)
+        if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(src), hdr_t):
+            _run([hipcc, *flags_for(src), "-c", src, "-o", obj], f"hipcc failed for {src}", verbose)
         return obj
 
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as ex:
         all_objs = list(ex.map(compile_one, sources() + contrib_sources()))
     objs, cobjs = all_objs[:len(sources())], all_objs[len(sources()):]
-    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB + ".tmp", *objs]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+    _run([*link, LIB + ".tmp", *objs], "link failed", verbose)
     os.replace(LIB + ".tmp", LIB)
     # the out-of-scope presses' kernels: resolved against the product library next to it ($ORIGIN)
-    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", CONTRIB_LIB + ".tmp", *cobjs,
-           "-L" + LIBDIR, "-l:libkvpress_hip.so", "-Wl,-rpath,$ORIGIN"]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"link failed (contrib):\n{r.stdout}\n{r.stderr}")
+    _run([*link, CONTRIB_LIB + ".tmp", *cobjs, "-L" + LIBDIR, "-l:libkvpress_hip.so", "-Wl,-rpath,$ORIGIN"], "link failed (contrib)", verbose)
     os.replace(CONTRIB_LIB + ".tmp", CONTRIB_LIB)
     # the fault-injection twin (tests only)
     src = os.path.join(CSRC, "topk_cluster.hip")
     fobj = os.path.join(OBJDIR, "topk_cluster.faultinject.obj")
-    cmd = [hipcc, *flags_for(src), "-DKVP_TC_FAULT_INJECTION", "-c", src, "-o", fobj]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"hipcc failed for {src} (fault injection):\n{r.stdout}\n{r.stderr}")
+    _run([hipcc, *flags_for(src), "-DKVP_TC_FAULT_INJECTION", "-c", src, "-o", fobj], f"hipcc failed for {src} (fault injection)", verbose)
     fobjs = [fobj if os.path.basename(o) == "topk_cluster.o" else o for o in objs]
-    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", FAULT_LIB + ".tmp", *fobjs]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"link failed (fault injection):\n{r.stdout}\n{r.stderr}")
+    _run([*link, FAULT_LIB + ".tmp", *fobjs], "link failed (fault injection)", verbose)
     os.replace(FAULT_LIB + ".tmp", FAULT_LIB)
     return LIB
 

@@ -805,7 +805,7 @@ extern "C" int kvp_ncattn_score(const void* q, int64_t q_sb, int64_t q_sh, int64
                                 int64_t v_sh, int64_t v_ss, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t D,
                                 int64_t chunk, float* raw, float* scores, void* ws, size_t ws_bytes, kvp_stream_t stream) {
     KVP_CHECK_ARG(q && cos && sin && k && v && scores && ws, "kvp_ncattn_score: null pointer");
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "kvp_ncattn_score: bad dtype %d", dtype);
+    KVP_CHECK_DTYPE("kvp_ncattn_score", dtype);
     KVP_CHECK_ARG(chunk >= 1, "kvp_ncattn_score: chunk_size must be positive (got %lld)", (long long)chunk);
     KVP_CHECK_ARG(B >= 1 && Hkv >= 1 && Hq >= Hkv && Hq % Hkv == 0, "kvp_ncattn_score: bad shape (Hq %% Hkv != 0: Hq=%lld Hkv=%lld)",
                   (long long)Hq, (long long)Hkv);
@@ -824,11 +824,7 @@ extern "C" int kvp_ncattn_score(const void* q, int64_t q_sb, int64_t q_sh, int64
     const bool mfma = nc_mfma_ok(dtype, D, chunk, G, k, k_sb, k_sh, k_ss, q_sh, q_ss, cs_ss, v_ss);
     const dim3 grid((unsigned)nchunks, (unsigned)Hkv, (unsigned)B);
     int rc;
-    switch (dtype) {
-        case KVP_F32: rc = nc_run<KVP_F32>(false, grid, st, q, q_sb, q_sh, q_ss, cos, sin, cs_sb, cs_ss, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, (int)Hkv, (int)G, (int)S, (int)chunk, (int)D, tmp); break;
-        case KVP_F16: rc = nc_run<KVP_F16>(mfma, grid, st, q, q_sb, q_sh, q_ss, cos, sin, cs_sb, cs_ss, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, (int)Hkv, (int)G, (int)S, (int)chunk, (int)D, tmp); break;
-        default: rc = nc_run<KVP_BF16>(mfma, grid, st, q, q_sb, q_sh, q_ss, cos, sin, cs_sb, cs_ss, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, (int)Hkv, (int)G, (int)S, (int)chunk, (int)D, tmp); break;
-    }
+    KVP_DISPATCH_DTYPE(dtype, rc = nc_run<DT>(mfma, grid, st, q, q_sb, q_sh, q_ss, cos, sin, cs_sb, cs_ss, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, (int)Hkv, (int)G, (int)S, (int)chunk, (int)D, tmp));   // (mfma is false for float32: nc_mfma_ok)
     if (rc != KVP_OK) return rc;
     return zscore_launch(tmp, rawp, B * Hkv * S, S, 1, scores, zw, st);
 }
@@ -842,7 +838,7 @@ extern "C" int kvp_leverage_score(const void* k, int64_t k_sb, int64_t k_sh, int
                                   int64_t p_sd, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, int64_t sketch, float* raw,
                                   float* scores, void* ws, size_t ws_bytes, kvp_stream_t stream) {
     KVP_CHECK_ARG(k && phi && scores && ws, "kvp_leverage_score: null pointer");
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "kvp_leverage_score: bad dtype %d", dtype);
+    KVP_CHECK_DTYPE("kvp_leverage_score", dtype);
     KVP_CHECK_ARG(sketch >= 1 && sketch <= 256, "kvp_leverage_score: sketch_dimension must be in [1, 256] (got %lld)", (long long)sketch);
     KVP_CHECK_ARG(B >= 1 && H >= 1 && B * H <= 65535 && S >= 1 && S < (1LL << 31) && D >= 1 && D <= 256,
                   "kvp_leverage_score: bad shape (B=%lld H=%lld S=%lld D=%lld; D <= 256)", (long long)B, (long long)H, (long long)S, (long long)D);
@@ -851,11 +847,7 @@ extern "C" int kvp_leverage_score(const void* k, int64_t k_sb, int64_t k_sh, int
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)ws;
     float* rawp = raw ? raw : (float*)(w + L.raw);
-    switch (dtype) {
-        case KVP_F32: lv_run<KVP_F32>(L, w, st, k, k_sb, k_sh, k_ss, phi, p_sb, p_sh, p_sd, (int)B, (int)H, (int)S, (int)D, (int)sketch, rawp); break;
-        case KVP_F16: lv_run<KVP_F16>(L, w, st, k, k_sb, k_sh, k_ss, phi, p_sb, p_sh, p_sd, (int)B, (int)H, (int)S, (int)D, (int)sketch, rawp); break;
-        default: lv_run<KVP_BF16>(L, w, st, k, k_sb, k_sh, k_ss, phi, p_sb, p_sh, p_sd, (int)B, (int)H, (int)S, (int)D, (int)sketch, rawp); break;
-    }
+    KVP_DISPATCH_DTYPE(dtype, lv_run<DT>(L, w, st, k, k_sb, k_sh, k_ss, phi, p_sb, p_sh, p_sd, (int)B, (int)H, (int)S, (int)D, (int)sketch, rawp));
     KVP_CHECK_LAUNCH("kvp_leverage_score");
     ZsWs zw{(double*)(w + L.zs), (double*)(w + L.zs) + ZS_BLOCKS};
     return zscore_launch(rawp, rawp, B * H * S, S, 0, scores, zw, st);

@@ -14,7 +14,9 @@
 // over the <= 1024 tokens of the partition in LDS.  K and V are each read twice (as reference and as data): HBM / L2 bound.
 // Ranks are exact integers; equal scores rank by position (torch.argsort leaves their order open).
 #include "../kvp_common.h"
+#pragma GCC visibility push(default)   // this library's C ABI
 #include "../../../include/kvpress_hip_extra.h"
+#pragma GCC visibility pop
 
 namespace {
 
@@ -269,7 +271,7 @@ extern "C" int kvp_lagkv_score(const void* k, int64_t k_sb, int64_t k_sh, int64_
                                int64_t v_ss, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, int64_t n_sink, int64_t lag_size,
                                int cross_scoring, float* scores, kvp_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "lagkv: bad dtype %d", dtype);
+    KVP_CHECK_DTYPE("lagkv", dtype);
     KVP_CHECK_ARG(B >= 1 && H >= 1 && D >= 2 && n_sink >= 0 && lag_size >= 1, "lagkv: bad shape B=%ld H=%ld D=%ld n_sink=%ld lag=%ld", (long)B,
                   (long)H, (long)D, (long)n_sink, (long)lag_size);
     KVP_CHECK_ARG(S >= n_sink + 2 * lag_size, "lagkv: needs at least n_sink + 2 * lag_size = %ld tokens (got %ld)", (long)(n_sink + 2 * lag_size), (long)S);
@@ -301,9 +303,7 @@ extern "C" int kvp_lagkv_score(const void* k, int64_t k_sb, int64_t k_sh, int64_
         KVP_LAUNCH("lagkv_score_vec_kernel", stream, (lagkv_score_vec_kernel<DT, L><<<grid, LG_THREADS, ldsv, stream>>>(a, chunks, scores))); \
         break;
 #define KVP_LG_DT(DT) switch (lpr) { KVP_LG_VEC(DT, 1) KVP_LG_VEC(DT, 2) KVP_LG_VEC(DT, 4) KVP_LG_VEC(DT, 8) KVP_LG_VEC(DT, 16) KVP_LG_VEC(DT, 32) KVP_LG_VEC(DT, 64) }
-        if (dtype == KVP_F32) { KVP_LG_DT(KVP_F32) }
-        else if (dtype == KVP_F16) { KVP_LG_DT(KVP_F16) }
-        else { KVP_LG_DT(KVP_BF16) }
+        KVP_DISPATCH_DTYPE(dtype, KVP_LG_DT(DT));
 #undef KVP_LG_DT
 #undef KVP_LG_VEC
         KVP_CHECK_LAUNCH("lagkv");
@@ -311,9 +311,7 @@ extern "C" int kvp_lagkv_score(const void* k, int64_t k_sb, int64_t k_sh, int64_
     }
     const size_t lds = ((size_t)2 * lag_size + (size_t)2 * LG_WAVES * D) * 4;
     if (a.n_scored) {
-        if (dtype == KVP_F32) KVP_LAUNCH("lagkv_score_kernel", stream, lagkv_score_kernel<KVP_F32><<<grid, LG_THREADS, lds, stream>>>(a, scores));
-        else if (dtype == KVP_F16) KVP_LAUNCH("lagkv_score_kernel", stream, lagkv_score_kernel<KVP_F16><<<grid, LG_THREADS, lds, stream>>>(a, scores));
-        else KVP_LAUNCH("lagkv_score_kernel", stream, lagkv_score_kernel<KVP_BF16><<<grid, LG_THREADS, lds, stream>>>(a, scores));
+        KVP_DISPATCH_DTYPE(dtype, KVP_LAUNCH("lagkv_score_kernel", stream, lagkv_score_kernel<DT><<<grid, LG_THREADS, lds, stream>>>(a, scores)));
     }
     KVP_CHECK_LAUNCH("lagkv");
     return KVP_OK;

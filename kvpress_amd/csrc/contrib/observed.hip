@@ -6,7 +6,9 @@
 // consecutive threads on consecutive columns (coalesced rows), four independent accumulators per thread over the query
 // rows; fp32 sums in a fixed order (no float atomics: deterministic).
 #include "../kvp_common.h"
+#pragma GCC visibility push(default)   // this library's C ABI
 #include "../../../include/kvpress_hip_extra.h"
+#pragma GCC visibility pop
 
 namespace {
 
@@ -43,7 +45,7 @@ __global__ __launch_bounds__(OA_THREADS) void observed_colmean_kernel(const type
 extern "C" int kvp_observed_attention_score(const void* attn, int64_t a_sb, int64_t a_sh, int64_t a_sq, int dtype, int64_t B, int64_t Hq,
                                             int64_t Hkv, int64_t Sq, int64_t S, float* scores, kvp_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "observed_attention: bad dtype %d", dtype);
+    KVP_CHECK_DTYPE("observed_attention", dtype);
     KVP_CHECK_ARG(B >= 1 && Hq >= 1 && Hkv >= 1 && Hq % Hkv == 0 && Sq >= 0 && S >= 0, "observed_attention: bad shape B=%ld Hq=%ld Hkv=%ld Sq=%ld S=%ld",
                   (long)B, (long)Hq, (long)Hkv, (long)Sq, (long)S);
     KVP_CHECK_ARG(S < ((int64_t)1 << 31) && Sq < ((int64_t)1 << 31) && B * Hkv <= 65535, "observed_attention: shape too large");
@@ -54,9 +56,7 @@ extern "C" int kvp_observed_attention_score(const void* attn, int64_t a_sb, int6
 #define KVP_OA(DT)                                                                                                                       \
     KVP_LAUNCH("observed_colmean_kernel", stream, observed_colmean_kernel<DT><<<dim3(bx, BH), OA_THREADS, 0, stream>>>(                 \
         static_cast<const Elem<DT>::T*>(attn), a_sb, a_sh, a_sq, (uint32_t)Hkv, (uint32_t)(Hq / Hkv), (uint32_t)Sq, (uint32_t)S, scores))
-    if (dtype == KVP_F32) KVP_OA(KVP_F32);
-    else if (dtype == KVP_F16) KVP_OA(KVP_F16);
-    else KVP_OA(KVP_BF16);
+    KVP_DISPATCH_DTYPE(dtype, KVP_OA(DT));
 #undef KVP_OA
     KVP_CHECK_LAUNCH("observed_attention");
     return KVP_OK;

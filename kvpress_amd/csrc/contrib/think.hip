@@ -6,7 +6,9 @@
 // Both are single streaming passes over K (HBM-bound): column sums of squares per (b, h) through per-workgroup partials
 // (fixed summation order, no float atomics), and a masked rewrite of the rows that carry a pruned channel.
 #include "../kvp_common.h"
+#pragma GCC visibility push(default)   // this library's C ABI
 #include "../../../include/kvpress_hip_extra.h"
+#pragma GCC visibility pop
 
 namespace {
 
@@ -139,16 +141,13 @@ extern "C" int kvp_think_channel_scores(const void* q, int64_t q_sb, int64_t q_s
                                         int64_t k_ss, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int64_t D,
                                         float* scores, void* ws, size_t ws_bytes, kvp_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "think: bad dtype %d", dtype);
+    KVP_CHECK_DTYPE("think", dtype);
     KVP_CHECK_ARG(B >= 1 && Hq >= 1 && Hkv >= 1 && Hq % Hkv == 0 && S >= 1 && W >= 1 && D >= 1 && D <= TH_THREADS,
                   "think: bad shape B=%ld Hq=%ld Hkv=%ld S=%ld W=%ld D=%ld (head_dim <= %d)", (long)B, (long)Hq, (long)Hkv, (long)S, (long)W, (long)D, TH_THREADS);
     KVP_CHECK_ARG(S < ((int64_t)1 << 31) && B * Hkv <= 65535, "think: shape too large");
     KVP_CHECK_ARG(q && k && scores, "think: null pointer");
     const size_t need = kvp_think_workspace_bytes(B, Hkv, S, D);
-    if (!ws || ws_bytes < need) {
-        kvp_set_error("think: workspace too small (%zu < %zu)", ws_bytes, need);
-        return KVP_EWORKSPACE;
-    }
+    if (int rc = kvp_check_workspace("think", ws, ws_bytes, need)) return rc;
     uint32_t nchunk = (uint32_t)((S + TH_ROWS - 1) / TH_ROWS);
     const uint32_t BH = (uint32_t)(B * Hkv);
     const size_t es = (size_t)kvp_elem_size(dtype), rowbytes = (size_t)D * es;
@@ -175,9 +174,7 @@ extern "C" int kvp_think_channel_scores(const void* q, int64_t q_sb, int64_t q_s
                                                                                                                  (uint32_t)Hkv, (uint32_t)S, (uint32_t)D, Dp, partial)); \
     KVP_LAUNCH("think_finish_kernel", stream, think_finish_kernel<DT><<<BH, TH_THREADS, 0, stream>>>(partial, nchunk, static_cast<const Elem<DT>::T*>(q), q_sb, q_sh, \
                                                                                                      q_sw, (uint32_t)Hkv, (uint32_t)(Hq / Hkv), (uint32_t)W, (uint32_t)S, (uint32_t)D, scores))
-    if (dtype == KVP_F32) { KVP_TH(KVP_F32); }
-    else if (dtype == KVP_F16) { KVP_TH(KVP_F16); }
-    else { KVP_TH(KVP_BF16); }
+    KVP_DISPATCH_DTYPE(dtype, KVP_TH(DT));
 #undef KVP_TH
 #undef KVP_TH_VEC
     KVP_CHECK_LAUNCH("think(channel scores)");
@@ -187,7 +184,7 @@ extern "C" int kvp_think_channel_scores(const void* q, int64_t q_sb, int64_t q_s
 extern "C" int kvp_zero_channels(void* x, int64_t sb, int64_t sh, int64_t ss, int dtype, int64_t B, int64_t H, int64_t S, int64_t D,
                                  const int32_t* idx, int64_t n, kvp_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "zero_channels: bad dtype %d", dtype);
+    KVP_CHECK_DTYPE("zero_channels", dtype);
     KVP_CHECK_ARG(B >= 0 && H >= 0 && S >= 0 && D >= 1 && n >= 0 && n <= 1024 && B * H <= 65535, "zero_channels: bad shape B=%ld H=%ld S=%ld D=%ld n=%ld",
                   (long)B, (long)H, (long)S, (long)D, (long)n);
     if (B * H * S * n == 0) return KVP_OK;
@@ -196,9 +193,7 @@ extern "C" int kvp_zero_channels(void* x, int64_t sb, int64_t sh, int64_t ss, in
 #define KVP_ZC(DT)                                                                                                                             \
     KVP_LAUNCH("zero_channels_kernel", stream, zero_channels_kernel<DT><<<dim3(bx, (uint32_t)(B * H)), TH_THREADS, 0, stream>>>(static_cast<Elem<DT>::T*>(x), sb, sh, ss, \
                                                                                                                                   (uint32_t)H, (uint32_t)S, (uint32_t)D, idx, (uint32_t)n))
-    if (dtype == KVP_F32) KVP_ZC(KVP_F32);
-    else if (dtype == KVP_F16) KVP_ZC(KVP_F16);
-    else KVP_ZC(KVP_BF16);
+    KVP_DISPATCH_DTYPE(dtype, KVP_ZC(DT));
 #undef KVP_ZC
     KVP_CHECK_LAUNCH("zero_channels");
     return KVP_OK;

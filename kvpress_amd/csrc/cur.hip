@@ -8,9 +8,6 @@
 // deterministic), fp32 throughout.  (One workgroup per row, as first written, took 400 us of the 490 us at 8 x 131072.)
 #include "kvp_common.h"
 
-int kvp_rowsumsq2_launch(const void* k, const void* v, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, int64_t k_sb, int64_t k_sh, int64_t k_ss,
-                         int64_t v_sb, int64_t v_sh, int64_t v_ss, float* out_k, float* out_v, hipStream_t stream);
-
 namespace {
 
 constexpr int CU_THREADS = 256;
@@ -135,13 +132,10 @@ extern "C" int kvp_cur_score(const void* k, int64_t k_sb, int64_t k_sh, int64_t 
     KVP_CHECK_ARG(k && v && scores, "cur: null pointer");
     const size_t half = kvp_align_up((size_t)B * H * S * 4, 256);
     const size_t need = kvp_cur_workspace_bytes(B, H, S);
-    if (!ws || ws_bytes < need) {
-        kvp_set_error("cur: workspace too small (%zu < %zu)", ws_bytes, need);
-        return KVP_EWORKSPACE;
-    }
+    if (int rc = kvp_check_workspace("cur", ws, ws_bytes, need)) return rc;
     float* k2 = static_cast<float*>(ws);
     float* v2 = reinterpret_cast<float*>(static_cast<char*>(ws) + half);
-    if (int rc = kvp_rowsumsq2_launch(k, v, dtype, B, H, S, D, k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, k2, v2, stream)) return rc;
+    if (int rc = kvp_rowsumsq2_launch({k, k_sb, k_sh, k_ss}, {v, v_sb, v_sh, v_ss}, dtype, B, H, S, D, k2, v2, stream)) return rc;
     float* partial = reinterpret_cast<float*>(static_cast<char*>(ws) + 2 * half);
     const uint32_t R = (uint32_t)(B * H);
     const uint32_t nblk = (uint32_t)std::max<int64_t>(1, std::min<int64_t>({(S + CU_THREADS - 1) / CU_THREADS, (int64_t)CU_MAXBLK, std::max<int64_t>(1, 2048 / R)}));

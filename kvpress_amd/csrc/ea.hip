@@ -16,9 +16,6 @@
 #include "softmax_stats.h"
 #include "ea_internal.h"
 
-int kvp_rownorm_launch_read_once(const void* x, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, int64_t sb, int64_t sh, int64_t ss,
-                                 float scale, float* out, hipStream_t stream);
-
 namespace {
 
 constexpr int EA_THREADS = 256;
@@ -401,16 +398,13 @@ extern "C" size_t kvp_ea_qstats_workspace_bytes(int64_t B, int64_t Hq, int64_t S
 extern "C" int kvp_ea_qstats(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, int dtype, int64_t B, int64_t Hq,
                              int64_t Sq, int64_t D, float* mu, float* cov, void* ws, size_t ws_bytes, kvp_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "ea_qstats: bad dtype %d", dtype);
+    KVP_CHECK_DTYPE("ea_qstats", dtype);
     KVP_CHECK_ARG(B >= 1 && Hq >= 1 && Sq >= 1 && D >= 1 && D <= 1024, "ea_qstats: bad shape B=%ld Hq=%ld Sq=%ld D=%ld",
                   (long)B, (long)Hq, (long)Sq, (long)D);
     KVP_CHECK_ARG(B <= 65535 && Hq <= 65535 && Sq < ((int64_t)1 << 31), "ea_qstats: shape too large");
     KVP_CHECK_ARG(q && mu, "ea_qstats: null pointer");
     const size_t need = kvp_ea_qstats_workspace_bytes(B, Hq, Sq, D);
-    if (!ws || ws_bytes < need) {
-        kvp_set_error("ea_qstats: workspace too small (%zu < %zu)", ws_bytes, need);
-        return KVP_EWORKSPACE;
-    }
+    if (int rc = kvp_check_workspace("ea_qstats", ws, ws_bytes, need)) return rc;
     if (ea_mfma_qstats_eligible(q, q_sb, q_sh, q_ss, dtype, Hq, Sq, D))
         return ea_mfma_qstats(q, q_sb, q_sh, q_ss, dtype, B, Hq, Sq, D, mu, cov, ws, stream);
 
@@ -431,9 +425,7 @@ extern "C" int kvp_ea_qstats(const void* q, int64_t q_sb, int64_t q_sh, int64_t 
             KVP_LAUNCH("ea_cov_finalize", stream, ea_cov_finalize<<<(uint32_t)((tot_cov + 255) / 256), 256, 0, stream>>>(w.pcov, w.nchunk_cov, (uint32_t)(D * D), inv_n, tot_cov, cov)); \
         }                                                                                                             \
     }
-    if (dtype == KVP_F32) KVP_EA_STATS(KVP_F32)
-    else if (dtype == KVP_F16) KVP_EA_STATS(KVP_F16)
-    else KVP_EA_STATS(KVP_BF16)
+    KVP_DISPATCH_DTYPE(dtype, KVP_EA_STATS(DT));
 #undef KVP_EA_STATS
     KVP_CHECK_LAUNCH("ea_qstats");
     return KVP_OK;
@@ -449,16 +441,13 @@ extern "C" int kvp_ea_score(const void* k, int64_t k_sb, int64_t k_sh, int64_t k
                             int64_t S, int64_t D, int64_t n_sink, int use_vnorm, float epsilon, float* scores, void* ws,
                             size_t ws_bytes, kvp_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "ea_score: bad dtype %d", dtype);
+    KVP_CHECK_DTYPE("ea_score", dtype);
     KVP_CHECK_ARG(B >= 1 && Hq >= 1 && Hkv >= 1 && Hq % Hkv == 0 && D >= 1 && D <= 1024, "ea_score: bad shape");
     KVP_CHECK_ARG(n_sink >= 0 && S > n_sink, "ea_score: Input should contain more tokens than n_sink=%ld", (long)n_sink);
     KVP_CHECK_ARG(S < ((int64_t)1 << 31) && B <= 65535 && Hq <= 65535, "ea_score: shape too large");
     KVP_CHECK_ARG(k && mu && scores && (v || !use_vnorm), "ea_score: null pointer");
     EaScoreWs w = carve_score_ws(ws, B, Hq, Hkv, S, D);
-    if (!ws || ws_bytes < w.total_bytes) {
-        kvp_set_error("ea_score: workspace too small (%zu < %zu)", ws_bytes, w.total_bytes);
-        return KVP_EWORKSPACE;
-    }
+    if (int rc = kvp_check_workspace("ea_score", ws, ws_bytes, w.total_bytes)) return rc;
     const int64_t Sp = S - n_sink;
     EaArgs a;
     a.k = k; a.k_sb = k_sb; a.k_sh = k_sh; a.k_ss = k_ss;
@@ -485,9 +474,7 @@ extern "C" int kvp_ea_score(const void* k, int64_t k_sb, int64_t k_sh, int64_t k
             }
         }
         const dim3 grid(nblk, (uint32_t)Hq, (uint32_t)B);
-        if (dtype == KVP_F32) KVP_LAUNCH("ea_logits_generic", stream, ea_logits_generic<KVP_F32><<<grid, EA_THREADS, lds, stream>>>(a, w.logits, nblk, w.part_m, w.part_z));
-        else if (dtype == KVP_F16) KVP_LAUNCH("ea_logits_generic", stream, ea_logits_generic<KVP_F16><<<grid, EA_THREADS, lds, stream>>>(a, w.logits, nblk, w.part_m, w.part_z));
-        else KVP_LAUNCH("ea_logits_generic", stream, ea_logits_generic<KVP_BF16><<<grid, EA_THREADS, lds, stream>>>(a, w.logits, nblk, w.part_m, w.part_z));
+        KVP_DISPATCH_DTYPE(dtype, KVP_LAUNCH("ea_logits_generic", stream, ea_logits_generic<DT><<<grid, EA_THREADS, lds, stream>>>(a, w.logits, nblk, w.part_m, w.part_z)));
     }
     const uint32_t nrows = (uint32_t)(B * Hq);
     const int64_t es = kvp_elem_size(dtype);
@@ -515,7 +502,7 @@ extern "C" int kvp_ea_score(const void* k, int64_t k_sb, int64_t k_sh, int64_t k
     KVP_CHECK_LAUNCH("ea_score(logits)");
     if (use_vnorm) {
         const char* vp = static_cast<const char*>(v) + n_sink * v_ss * kvp_elem_size(dtype);
-        if (int rc = kvp_rownorm_launch_read_once(vp, dtype, B, Hkv, Sp, D, v_sb, v_sh, v_ss, 1.0f, w.vnorm, stream)) return rc;
+        if (int rc = kvp_rownorm_launch_read_once({vp, v_sb, v_sh, v_ss}, dtype, B, Hkv, Sp, D, 1.0f, w.vnorm, stream)) return rc;
     }
     const uint64_t total = (uint64_t)B * Hkv * Sp;
     const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((total + EA_THREADS - 1) / EA_THREADS, 2048));

@@ -118,7 +118,7 @@ extern "C" int kvp_gather_kv(const void* k, int64_t k_sb, int64_t k_sh, int64_t 
                              const int32_t* idx, int64_t n, void* k_out, void* v_out, kvp_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (int rc = kvp_async_check("kvp_gather_kv")) return rc;
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "gather: bad dtype %d", dtype);
+    KVP_CHECK_DTYPE("gather", dtype);
     KVP_CHECK_ARG(B >= 0 && H >= 0 && S >= 0 && D >= 1 && n >= 0 && n <= S, "gather: bad shape B=%ld H=%ld S=%ld D=%ld n=%ld",
                   (long)B, (long)H, (long)S, (long)D, (long)n);
     const int64_t nrows64 = B * H * n;

@@ -321,7 +321,7 @@ extern "C" size_t kvp_keydiff_workspace_bytes(int64_t B, int64_t H, int64_t S, i
 extern "C" int kvp_keydiff_score(const void* k, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, int64_t sb, int64_t sh,
                                  int64_t ss, float* scores, void* ws, size_t ws_bytes, kvp_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "keydiff: bad dtype %d", dtype);
+    KVP_CHECK_DTYPE("keydiff", dtype);
     KVP_CHECK_ARG(B >= 0 && H >= 0 && S >= 0 && D >= 1 && D <= 8192, "keydiff: bad shape B=%ld H=%ld S=%ld D=%ld", (long)B, (long)H,
                   (long)S, (long)D);
     if (B * H * S == 0) return KVP_OK;
@@ -329,19 +329,12 @@ extern "C" int kvp_keydiff_score(const void* k, int dtype, int64_t B, int64_t H,
     KVP_CHECK_ARG(S < ((int64_t)1 << 31) && B * H <= 65535, "keydiff: shape too large (S=%ld, B*H=%ld)", (long)S, (long)(B * H));
     size_t poff = 0;
     const size_t need = keydiff_ws(B * H, S, D, &poff);
-    if (!ws || ws_bytes < need) {
-        kvp_set_error("keydiff: workspace too small (%zu < %zu)", ws_bytes, need);
-        return KVP_EWORKSPACE;
-    }
+    if (int rc = kvp_check_workspace("keydiff", ws, ws_bytes, need)) return rc;
     float* anchor = static_cast<float*>(ws);
     float* partial = reinterpret_cast<float*>(static_cast<char*>(ws) + poff);
     KdMap map{(uint32_t)H, (uint32_t)S, sb, sh, ss};
     const uint32_t BH = (uint32_t)(B * H);
-    switch (dtype) {
-        case KVP_F32: launch_keydiff<KVP_F32>(k, map, BH, (uint32_t)D, scores, anchor, partial, stream); break;
-        case KVP_F16: launch_keydiff<KVP_F16>(k, map, BH, (uint32_t)D, scores, anchor, partial, stream); break;
-        default: launch_keydiff<KVP_BF16>(k, map, BH, (uint32_t)D, scores, anchor, partial, stream); break;
-    }
+    KVP_DISPATCH_DTYPE(dtype, launch_keydiff<DT>(k, map, BH, (uint32_t)D, scores, anchor, partial, stream));
     KVP_CHECK_LAUNCH("keydiff");
     return KVP_OK;
 }

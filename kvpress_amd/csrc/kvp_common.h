@@ -6,51 +6,12 @@
 
 #include <algorithm>
 
+#pragma GCC visibility push(default)   // the C ABI: the only symbols the library exports on purpose (besides KVP_INTERNAL_API, kvp_host.h)
 #include "../../include/kvpress_hip.h"
 #include "../../include/kvpress_hip_lab.h"
+#pragma GCC visibility pop
 
-// ---- error reporting (thread-local last message; defined in capi.hip) ------------------------
-void kvp_set_error(const char* fmt, ...);
-
-#define KVP_CHECK_ARG(cond, ...)                 \
-    do {                                         \
-        if (!(cond)) {                           \
-            kvp_set_error(__VA_ARGS__);          \
-            return KVP_EINVAL;                   \
-        }                                        \
-    } while (0)
-
-#define KVP_CHECK_LAUNCH(name)                                                     \
-    do {                                                                           \
-        hipError_t e__ = hipGetLastError();                                        \
-        if (e__ != hipSuccess) {                                                   \
-            kvp_set_error("%s: launch failed: %s", name, hipGetErrorString(e__));  \
-            return KVP_EHIP;                                                       \
-        }                                                                          \
-    } while (0)
-
-// ---- asynchronous failure reports (capi.hip) -------------------------------------------------------------------------------
-// A kernel that detects at RUN time that its result is invalid (the cluster select when its workgroups never become co-resident,
-// topk_cluster.hip) poisons its output AND stores a code into one process-wide, host-pinned status word; every entry point that
-// produces or consumes a selection calls kvp_async_check() first and turns a pending report into KVP_EASYNC + kvp_last_error().
-// The word holds (launch sequence number << 8) | code: all the stores of ONE failed launch make one report, however late the last of
-// them lands (a repeat of a sequence number that was already reported is dropped).
-uint32_t* kvp_async_flag();             // device-visible address of the status word (nullptr: pinned allocation failed -> poison only)
-uint32_t kvp_async_next_seq();          // sequence number (1 .. 2^24 - 1, wrapping) for the next launch that may report
-int kvp_async_check(const char* who);   // KVP_OK, or KVP_EASYNC exactly once per report
-
-// ---- opt-in per-kernel timing (kvp_prof_* in include/kvpress_hip.h; implemented in capi.hip) ----
-bool kvp_prof_enabled();
-void kvp_prof_begin(const char* name, hipStream_t stream);
-void kvp_prof_end(hipStream_t stream);
-// every kernel launch of the library goes through this macro
-#define KVP_LAUNCH(name, stream, ...)                         \
-    do {                                                      \
-        const bool prof__ = kvp_prof_enabled();               \
-        if (prof__) kvp_prof_begin(name, stream);             \
-        __VA_ARGS__;                                          \
-        if (prof__) kvp_prof_end(stream);                     \
-    } while (0)
+#include "kvp_host.h"
 
 static inline size_t kvp_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int kvp_elem_size(int dtype) { return dtype == KVP_F32 ? 4 : 2; }
@@ -141,9 +102,6 @@ template <bool NT> __device__ __forceinline__ void st16(void* p, const uint4& v)
         *reinterpret_cast<uint4*>(p) = v;
     }
 }
-
-// tuning knobs read from the environment once (KVP_* variables; used for A/B runs on hardware)
-int kvp_env_int(const char* name, int dflt);
 
 // ---- wave / block reductions -----------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {

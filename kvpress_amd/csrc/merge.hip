@@ -657,7 +657,7 @@ extern "C" int kvp_merge_values(const void* k, int64_t k_sb, int64_t k_sh, int64
                                 int64_t v_ss, const int32_t* kept_idx, const void* k_out, void* v_out, int dtype, int64_t B, int64_t H,
                                 int64_t S, int64_t n_kept, int64_t D, double similarity_threshold, double merge_fraction, void* ws,
                                 size_t ws_bytes, int32_t* target, float* max_sim, kvp_stream_t stream) {
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "kvp_merge_values: bad dtype %d", dtype);
+    KVP_CHECK_DTYPE("kvp_merge_values", dtype);
     KVP_CHECK_ARG(B >= 1 && H >= 1 && S >= 1 && D >= 1 && n_kept >= 0 && n_kept <= S, "kvp_merge_values: bad shape");
     KVP_CHECK_ARG(S < ((int64_t)1 << 31) / 2 && B * H < 65536, "kvp_merge_values: bad shape (S, B * H too large)");
     KVP_CHECK_ARG(D <= 256, "kvp_merge_values: head size %lld > 256 is not supported", (long long)D);
@@ -666,17 +666,10 @@ extern "C" int kvp_merge_values(const void* k, int64_t k_sb, int64_t k_sh, int64
     if (ne == 0 || n_kept == 0) return KVP_OK;   // merging_press.py:120-121: nothing to merge
     KVP_CHECK_ARG(k && v && kept_idx && k_out && v_out && ws, "kvp_merge_values: null pointer");
     const MrgLayout L = mrg_layout(B * H, S);
-    if (ws_bytes < L.total) {
-        kvp_set_error("kvp_merge_values: workspace too small (%zu < %zu)", ws_bytes, L.total);
-        return KVP_EWORKSPACE;
-    }
+    if (int rc = kvp_check_workspace("kvp_merge_values", ws, ws_bytes, L.total)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const float thr = (float)similarity_threshold;          // `max_sim >= threshold` compares in float32
     const float q = (float)(1.0 - merge_fraction);          // torch.quantile's q tensor has the input's dtype
     const bool frac = merge_fraction < 1.0;
-    switch (dtype) {
-        case KVP_F32: return mrg_run<KVP_F32>(L, (char*)ws, st, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, kept_idx, k_out, v_out, B, H, S, n_kept, D, thr, q, frac, target, max_sim);
-        case KVP_F16: return mrg_run<KVP_F16>(L, (char*)ws, st, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, kept_idx, k_out, v_out, B, H, S, n_kept, D, thr, q, frac, target, max_sim);
-        default: return mrg_run<KVP_BF16>(L, (char*)ws, st, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, kept_idx, k_out, v_out, B, H, S, n_kept, D, thr, q, frac, target, max_sim);
-    }
+    KVP_DISPATCH_DTYPE(dtype, return mrg_run<DT>(L, (char*)ws, st, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, kept_idx, k_out, v_out, B, H, S, n_kept, D, thr, q, frac, target, max_sim));
 }

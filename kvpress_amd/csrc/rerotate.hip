@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void gather_rerotate_kernel(GrArgs a) {
 extern "C" int kvp_rerotate_keys(void* k, int dtype, int64_t B, int64_t H, int64_t n, int64_t D, const int32_t* idx,
                                  const float* inv_freq, kvp_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "rerotate: bad dtype %d", dtype);
+    KVP_CHECK_DTYPE("rerotate", dtype);
     KVP_CHECK_ARG(B >= 0 && H >= 0 && n >= 0 && D >= 2 && D % 2 == 0, "rerotate: bad shape B=%ld H=%ld n=%ld D=%ld", (long)B, (long)H,
                   (long)n, (long)D);
     if (B * H * n == 0) return KVP_OK;
@@ -202,25 +202,17 @@ extern "C" int kvp_rerotate_keys(void* k, int dtype, int64_t B, int64_t H, int64
         KVP_CHECK_LAUNCH("rerotate");
         return KVP_OK;
     }
-    switch (dtype) {
-        case KVP_F32: KVP_LAUNCH("rerotate_kernel", stream, rerotate_kernel<KVP_F32><<<dim3(bx, BH), 256, 0, stream>>>(static_cast<float*>(k), idx, inv_freq, (uint32_t)n, (uint32_t)D)); break;
-        case KVP_F16: KVP_LAUNCH("rerotate_kernel", stream, rerotate_kernel<KVP_F16><<<dim3(bx, BH), 256, 0, stream>>>(static_cast<_Float16*>(k), idx, inv_freq, (uint32_t)n, (uint32_t)D)); break;
-        default: KVP_LAUNCH("rerotate_kernel", stream, rerotate_kernel<KVP_BF16><<<dim3(bx, BH), 256, 0, stream>>>(static_cast<uint16_t*>(k), idx, inv_freq, (uint32_t)n, (uint32_t)D)); break;
-    }
+    KVP_DISPATCH_DTYPE(dtype, KVP_LAUNCH("rerotate_kernel", stream, rerotate_kernel<DT><<<dim3(bx, BH), 256, 0, stream>>>(static_cast<Elem<DT>::T*>(k), idx, inv_freq, (uint32_t)n, (uint32_t)D)));
     KVP_CHECK_LAUNCH("rerotate");
     return KVP_OK;
 }
-
-extern "C" int kvp_gather_kv(const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* v, int64_t v_sb, int64_t v_sh, int64_t v_ss,
-                             int dtype, int64_t B, int64_t H, int64_t S, int64_t D, const int32_t* idx, int64_t n, void* k_out, void* v_out,
-                             kvp_stream_t stream);
 
 extern "C" int kvp_gather_kv_rerotate(const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* v, int64_t v_sb, int64_t v_sh,
                                       int64_t v_ss, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, const int32_t* idx, int64_t n,
                                       const float* inv_freq, void* k_out, void* v_out, kvp_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (int rc = kvp_async_check("kvp_gather_kv_rerotate")) return rc;
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "gather_rerotate: bad dtype %d", dtype);
+    KVP_CHECK_DTYPE("gather_rerotate", dtype);
     KVP_CHECK_ARG(B >= 0 && H >= 0 && S >= 0 && D >= 2 && D % 2 == 0 && n >= 0 && n <= S, "gather_rerotate: bad shape B=%ld H=%ld S=%ld D=%ld n=%ld",
                   (long)B, (long)H, (long)S, (long)D, (long)n);
     if (B * H * n == 0) return KVP_OK;

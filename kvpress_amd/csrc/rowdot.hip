@@ -122,17 +122,13 @@ void launch_rowdot(const void* x, uint32_t BH, uint32_t H, uint32_t S, uint32_t 
 extern "C" int kvp_rowdot_score(const void* x, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, int64_t sb, int64_t sh,
                                 int64_t ss, const void* filt, int64_t f_sh, float scale, float* out, kvp_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "rowdot: bad dtype %d", dtype);
+    KVP_CHECK_DTYPE("rowdot", dtype);
     KVP_CHECK_ARG(B >= 0 && H >= 0 && S >= 0 && D >= 1, "rowdot: bad shape B=%ld H=%ld S=%ld D=%ld", (long)B, (long)H, (long)S, (long)D);
     if (B * H * S == 0) return KVP_OK;
     KVP_CHECK_ARG(x && filt && out, "rowdot: null pointer");
     KVP_CHECK_ARG(S < ((int64_t)1 << 31) && B * H <= 65535, "rowdot: shape too large (S=%ld, B*H=%ld)", (long)S, (long)(B * H));
     const uint32_t BH = (uint32_t)(B * H);
-    switch (dtype) {
-        case KVP_F32: launch_rowdot<KVP_F32>(x, BH, (uint32_t)H, (uint32_t)S, (uint32_t)D, sb, sh, ss, filt, f_sh, scale, out, stream); break;
-        case KVP_F16: launch_rowdot<KVP_F16>(x, BH, (uint32_t)H, (uint32_t)S, (uint32_t)D, sb, sh, ss, filt, f_sh, scale, out, stream); break;
-        default: launch_rowdot<KVP_BF16>(x, BH, (uint32_t)H, (uint32_t)S, (uint32_t)D, sb, sh, ss, filt, f_sh, scale, out, stream); break;
-    }
+    KVP_DISPATCH_DTYPE(dtype, launch_rowdot<DT>(x, BH, (uint32_t)H, (uint32_t)S, (uint32_t)D, sb, sh, ss, filt, f_sh, scale, out, stream));
     KVP_CHECK_LAUNCH("rowdot");
     return KVP_OK;
 }

@@ -268,63 +268,55 @@ int launch_rownorm(const void* x, PlaneMap map, uint32_t BH, uint32_t D, float s
 // Internal entry shared with the ExpectedAttention path (||V||) and the fused Knorm compress.
 // hist1 (nullable): [B*H][4096] first-pass radix histogram of the top-k over the rows (b, h); *hist1_done tells whether it
 // was produced (only the vector path does; the caller runs the separate pass otherwise).
-static int rownorm_launch_impl(const void* x, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, int64_t sb, int64_t sh,
-                               int64_t ss, float scale, float* out, hipStream_t stream, uint32_t* hist1, bool* hist1_done, bool squared, bool read_once) {
+static int rownorm_launch_impl(KvpRows x, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, float scale, float* out, hipStream_t stream,
+                               uint32_t* hist1, bool* hist1_done, bool squared, bool read_once) {
     if (hist1_done) *hist1_done = false;
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "rownorm: bad dtype %d", dtype);
+    KVP_CHECK_DTYPE("rownorm", dtype);
     KVP_CHECK_ARG(B >= 0 && H >= 0 && S >= 0 && D >= 1, "rownorm: bad shape B=%ld H=%ld S=%ld D=%ld", (long)B, (long)H,
                   (long)S, (long)D);
     const int64_t nrows64 = B * H * S;
     if (nrows64 == 0) return KVP_OK;
-    KVP_CHECK_ARG(x && out, "rownorm: null pointer");
+    KVP_CHECK_ARG(x.p && out, "rownorm: null pointer");
     // collapse (h, s) and (b, h) when the view is contiguous across them: fewer, longer planes
     // (not with a fused histogram: its rows are the (b, h) planes)
-    if (!hist1 && H > 1 && sh == S * ss) { S *= H; H = 1; sh = 0; }
-    if (!hist1 && H == 1 && B > 1 && sb == S * ss) { S *= B; B = 1; sb = 0; }
+    if (!hist1 && H > 1 && x.sh == S * x.ss) { S *= H; H = 1; x.sh = 0; }
+    if (!hist1 && H == 1 && B > 1 && x.sb == S * x.ss) { S *= B; B = 1; x.sb = 0; }
     KVP_CHECK_ARG(S < ((int64_t)1 << 31) && B * H <= 65535, "rownorm: shape too large (S=%ld, B*H=%ld)", (long)S, (long)(B * H));
-    PlaneMap map{(uint32_t)H, (uint32_t)S, sb, sh, ss, squared};
+    PlaneMap map{(uint32_t)H, (uint32_t)S, x.sb, x.sh, x.ss, squared};
     const uint32_t BH = (uint32_t)(B * H);
     int done = 0;
-    switch (dtype) {
-        case KVP_F32: done = launch_rownorm<KVP_F32>(x, map, BH, (uint32_t)D, scale, out, hist1, stream, read_once); break;
-        case KVP_F16: done = launch_rownorm<KVP_F16>(x, map, BH, (uint32_t)D, scale, out, hist1, stream, read_once); break;
-        default: done = launch_rownorm<KVP_BF16>(x, map, BH, (uint32_t)D, scale, out, hist1, stream, read_once); break;
-    }
+    KVP_DISPATCH_DTYPE(dtype, done = launch_rownorm<DT>(x.p, map, BH, (uint32_t)D, scale, out, hist1, stream, read_once));
     if (hist1_done) *hist1_done = done != 0;
     KVP_CHECK_LAUNCH("rownorm");
     return KVP_OK;
 }
 
-int kvp_rownorm_launch(const void* x, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, int64_t sb, int64_t sh,
-                       int64_t ss, float scale, float* out, hipStream_t stream, uint32_t* hist1, bool* hist1_done) {
-    return rownorm_launch_impl(x, dtype, B, H, S, D, sb, sh, ss, scale, out, stream, hist1, hist1_done, false, false);
+int kvp_rownorm_launch(KvpRows x, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, float scale, float* out, hipStream_t stream,
+                       uint32_t* hist1, bool* hist1_done) {
+    return rownorm_launch_impl(x, dtype, B, H, S, D, scale, out, stream, hist1, hist1_done, false, false);
 }
 // the same for a tensor this path reads once (ExpectedAttention's ||V||): streaming loads when it is larger than the memory-side cache can hold
-int kvp_rownorm_launch_read_once(const void* x, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, int64_t sb, int64_t sh, int64_t ss,
-                                 float scale, float* out, hipStream_t stream) {
-    return rownorm_launch_impl(x, dtype, B, H, S, D, sb, sh, ss, scale, out, stream, nullptr, nullptr, false, true);
+int kvp_rownorm_launch_read_once(KvpRows x, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, float scale, float* out, hipStream_t stream) {
+    return rownorm_launch_impl(x, dtype, B, H, S, D, scale, out, stream, nullptr, nullptr, false, true);
 }
 // out[b,h,s] = sum_d x^2  (the row "energy" of CURPress, kvpress/presses/cur_press.py:40-41)
-int kvp_rowsumsq_launch(const void* x, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, int64_t sb, int64_t sh, int64_t ss,
-                        float* out, hipStream_t stream) {
-    return rownorm_launch_impl(x, dtype, B, H, S, D, sb, sh, ss, 1.0f, out, stream, nullptr, nullptr, true, false);
+static int kvp_rowsumsq_launch(KvpRows x, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, float* out, hipStream_t stream) {
+    return rownorm_launch_impl(x, dtype, B, H, S, D, 1.0f, out, stream, nullptr, nullptr, true, false);
 }
 
 // out_k[b,h,s] = sum_d k^2 and out_v likewise in one launch when both tensors take the 16-lanes-per-256-byte-row vector path (else two
 // launches of the general kernel).  Same values as kvp_rowsumsq_launch.
-int kvp_rowsumsq2_launch(const void* k, const void* v, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, int64_t k_sb, int64_t k_sh, int64_t k_ss,
-                         int64_t v_sb, int64_t v_sh, int64_t v_ss, float* out_k, float* out_v, hipStream_t stream) {
+int kvp_rowsumsq2_launch(KvpRows kr, KvpRows vr, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, float* out_k, float* out_v, hipStream_t stream) {
+    const void *k = kr.p, *v = vr.p;
     const int64_t es = kvp_elem_size(dtype);
-    auto al = [&](const void* p, int64_t sb, int64_t sh, int64_t ss) {
-        return ((uintptr_t)p % 16) == 0 && (sb * es) % 16 == 0 && (sh * es) % 16 == 0 && (ss * es) % 16 == 0;
-    };
+    auto al = [&](const KvpRows& r) { return ((uintptr_t)r.p % 16) == 0 && (r.sb * es) % 16 == 0 && (r.sh * es) % 16 == 0 && (r.ss * es) % 16 == 0; };
     const bool fast = (dtype == KVP_BF16 || dtype == KVP_F16) && D * es == 256 && B * H >= 1 && B * H <= 65535 && S >= 1 && S < ((int64_t)1 << 31) &&
-                      al(k, k_sb, k_sh, k_ss) && al(v, v_sb, v_sh, v_ss) && k && v && out_k && out_v;
+                      al(kr) && al(vr) && k && v && out_k && out_v;
     if (!fast) {
-        if (int rc = kvp_rowsumsq_launch(k, dtype, B, H, S, D, k_sb, k_sh, k_ss, out_k, stream)) return rc;
-        return kvp_rowsumsq_launch(v, dtype, B, H, S, D, v_sb, v_sh, v_ss, out_v, stream);
+        if (int rc = kvp_rowsumsq_launch(kr, dtype, B, H, S, D, out_k, stream)) return rc;
+        return kvp_rowsumsq_launch(vr, dtype, B, H, S, D, out_v, stream);
     }
-    PlaneMap mk{(uint32_t)H, (uint32_t)S, k_sb, k_sh, k_ss, true}, mv{(uint32_t)H, (uint32_t)S, v_sb, v_sh, v_ss, true};
+    PlaneMap mk{(uint32_t)H, (uint32_t)S, kr.sb, kr.sh, kr.ss, true}, mv{(uint32_t)H, (uint32_t)S, vr.sb, vr.sh, vr.ss, true};
     const uint32_t BH = (uint32_t)(B * H);
     if (S >= 4096) {
         const bool nts = rn_streaming((uint64_t)BH * 2 * S * 256, true);
@@ -348,5 +340,5 @@ int kvp_rowsumsq2_launch(const void* k, const void* v, int dtype, int64_t B, int
 
 extern "C" int kvp_rownorm_score(const void* x, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, int64_t sb,
                                  int64_t sh, int64_t ss, float scale, float* out, kvp_stream_t stream) {
-    return kvp_rownorm_launch(x, dtype, B, H, S, D, sb, sh, ss, scale, out, static_cast<hipStream_t>(stream), nullptr, nullptr);
+    return kvp_rownorm_launch({x, sb, sh, ss}, dtype, B, H, S, D, scale, out, static_cast<hipStream_t>(stream), nullptr, nullptr);
 }

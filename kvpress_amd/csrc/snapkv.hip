@@ -377,12 +377,15 @@ SnapWs carve_snap_ws(void* ws, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, in
 // hist1 != nullptr (fused compress): scores[.., :S-W] are written and histogrammed, the pad columns are NOT filled
 // finish = SNAP_FINISH_NO_PAD without hist1: the same, for a select that needs no histogram (short rows, topk_row_kernel);
 // SNAP_FINISH_COLSUM: nothing is launched, the caller selects straight from w.colsum (topk_select_pooled_rows)
-int finish_scores(const SnapWs& w, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int kernel_size,
-                  float* scores, hipStream_t stream, uint32_t* hist1 = nullptr, int finish = SNAP_FINISH_FULL) {
-    if (finish == SNAP_FINISH_COLSUM) return KVP_OK;
-    const bool skip_pad = finish != SNAP_FINISH_FULL;
-    const uint32_t BH = (uint32_t)(B * Hkv);
-    const float inv = snapkv_pool_scale(Hq, Hkv, W, kernel_size);
+int finish_scores(const SnapWs& w, const SnapCall& c) {
+    if (c.finish == SNAP_FINISH_COLSUM) return KVP_OK;
+    const int64_t S = c.S, W = c.W;
+    const int kernel_size = c.kernel_size;
+    float* scores = c.scores;
+    hipStream_t stream = c.stream;
+    const bool skip_pad = c.finish != SNAP_FINISH_FULL;
+    const uint32_t BH = (uint32_t)(c.B * c.Hkv);
+    const float inv = snapkv_pool_scale(c.Hq, c.Hkv, W, kernel_size);
     // four scores per thread: kernel_size 5, aligned row starts, long rows (short ones are launch-bound either way)
     const bool vec = kernel_size == 5 && (S - W) % 2 == 0 && S % 4 == 0 && ((uintptr_t)scores % 16) == 0 && S - W >= 8192;
     const uint64_t per_wg = (uint64_t)SK_THREADS * (vec ? 4 : 1);
@@ -390,9 +393,9 @@ int finish_scores(const SnapWs& w, int64_t B, int64_t Hq, int64_t Hkv, int64_t S
     const uint32_t bx = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)(S - W) + per_wg - 1) / per_wg, std::max<uint64_t>(1, std::min<uint64_t>(wg_cap, 4096) / BH)));
     const dim3 grid(bx, BH);
     const int pad = kernel_size / 2;
-    if (hist1) {
-        if (vec) KVP_LAUNCH("snapkv_pool_kernel", stream, snapkv_pool5_vec_kernel<true><<<grid, SK_THREADS, 0, stream>>>(w.colsum, (uint32_t)S, (uint32_t)W, inv, scores, w.bmax, hist1));
-        else KVP_LAUNCH("snapkv_pool_kernel", stream, snapkv_pool_kernel<true><<<grid, SK_THREADS, 0, stream>>>(w.colsum, (uint32_t)S, (uint32_t)W, pad, inv, scores, w.bmax, hist1));
+    if (c.hist1) {
+        if (vec) KVP_LAUNCH("snapkv_pool_kernel", stream, snapkv_pool5_vec_kernel<true><<<grid, SK_THREADS, 0, stream>>>(w.colsum, (uint32_t)S, (uint32_t)W, inv, scores, w.bmax, c.hist1));
+        else KVP_LAUNCH("snapkv_pool_kernel", stream, snapkv_pool_kernel<true><<<grid, SK_THREADS, 0, stream>>>(w.colsum, (uint32_t)S, (uint32_t)W, pad, inv, scores, w.bmax, c.hist1));
         KVP_CHECK_LAUNCH("snapkv(pool+hist)");
         return KVP_OK;
     }
@@ -408,47 +411,35 @@ int finish_scores(const SnapWs& w, int64_t B, int64_t Hq, int64_t Hkv, int64_t S
     return KVP_OK;
 }
 
-int check_common(int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int kernel_size) {
-    KVP_CHECK_ARG(B >= 1 && Hq >= 1 && Hkv >= 1 && Hq % Hkv == 0, "snapkv: bad heads B=%ld Hq=%ld Hkv=%ld", (long)B, (long)Hq, (long)Hkv);
-    KVP_CHECK_ARG(W >= 1 && S > W, "snapkv: query length %ld should be greater than the window size %ld", (long)S, (long)W);
-    KVP_CHECK_ARG(kernel_size >= 1 && (kernel_size & 1), "snapkv: kernel_size must be odd (got %d)", kernel_size);
-    KVP_CHECK_ARG(S < ((int64_t)1 << 31) && B * Hq <= 65535 && B <= 65535, "snapkv: shape too large");
+// the checks every entry starts with
+int check_common(const SnapCall& c) {
+    KVP_CHECK_DTYPE("snapkv", c.dtype);
+    KVP_CHECK_ARG(c.B >= 1 && c.Hq >= 1 && c.Hkv >= 1 && c.Hq % c.Hkv == 0, "snapkv: bad heads B=%ld Hq=%ld Hkv=%ld", (long)c.B, (long)c.Hq, (long)c.Hkv);
+    KVP_CHECK_ARG(c.W >= 1 && c.S > c.W, "snapkv: query length %ld should be greater than the window size %ld", (long)c.S, (long)c.W);
+    KVP_CHECK_ARG(c.kernel_size >= 1 && (c.kernel_size & 1), "snapkv: kernel_size must be odd (got %d)", c.kernel_size);
+    KVP_CHECK_ARG(c.S < ((int64_t)1 << 31) && c.B * c.Hq <= 65535 && c.B <= 65535, "snapkv: shape too large");
     return KVP_OK;
 }
 
-}  // namespace
+// the window queries that the RoPE / q_proj kernels left in the workspace, as a view for snapkv_score_impl
+KvpRows qrot_rows(const SnapWs& w, const SnapCall& c) { return {w.qrot, c.Hq * c.W * c.D, c.W * c.D, c.D}; }
 
-extern "C" size_t kvp_snapkv_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int64_t D) {
-    if (B < 1 || Hq < 1 || Hkv < 1 || S < 1 || W < 1 || D < 1) return 256;
-    return carve_snap_ws(nullptr, B, Hq, Hkv, S, W, D).total_bytes;
-}
-
-float* snapkv_ws_colsum(void* ws, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int64_t D) {
-    return carve_snap_ws(ws, B, Hq, Hkv, S, W, D).colsum;
-}
-float snapkv_pool_scale(int64_t Hq, int64_t Hkv, int64_t W, int kernel_size) {
-    return (float)(1.0 / ((double)(Hq / Hkv) * (double)W * (double)kernel_size));
-}
-
-int snapkv_score_impl(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_sw, const void* k, int64_t k_sb,
-                      int64_t k_sh, int64_t k_ss, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S,
-                      int64_t W, int64_t D, int kernel_size, float* scores, void* ws, size_t ws_bytes,
-                      hipStream_t stream, uint32_t* hist1, bool count_norm = false, int finish = SNAP_FINISH_FULL) {
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "snapkv: bad dtype %d", dtype);
-    if (int rc = check_common(B, Hq, Hkv, S, W, kernel_size)) return rc;
+// q: RoPE'd window queries [B,Hq,W,D]
+int snapkv_score_impl(const SnapCall& c, KvpRows q) {
+    const int64_t B = c.B, Hq = c.Hq, Hkv = c.Hkv, S = c.S, W = c.W, D = c.D;
+    const int dtype = c.dtype;
+    hipStream_t stream = c.stream;
+    if (int rc = check_common(c)) return rc;
     KVP_CHECK_ARG(D >= 1 && D <= 1024, "snapkv: unsupported head_dim %ld", (long)D);
-    const uint32_t norm_base = count_norm ? (uint32_t)(S - W) : 0;  // window row w sees S - W + w keys
-    KVP_CHECK_ARG(q && k && scores, "snapkv: null pointer");
-    SnapWs w = carve_snap_ws(ws, B, Hq, Hkv, S, W, D);
-    if (!ws || ws_bytes < w.total_bytes) {
-        kvp_set_error("snapkv: workspace too small (%zu < %zu)", ws_bytes, w.total_bytes);
-        return KVP_EWORKSPACE;
-    }
+    const uint32_t norm_base = c.count_norm ? (uint32_t)(S - W) : 0;  // window row w sees S - W + w keys
+    KVP_CHECK_ARG(q.p && c.k.p && c.scores, "snapkv: null pointer");
+    SnapWs w = carve_snap_ws(c.ws, B, Hq, Hkv, S, W, D);
+    if (int rc = kvp_check_workspace("snapkv", c.ws, c.ws_bytes, w.total_bytes)) return rc;
 
     SnapArgs a;
-    a.q = q; a.k = k;
-    a.q_sb = q_sb; a.q_sh = q_sh; a.q_sw = q_sw;
-    a.k_sb = k_sb; a.k_sh = k_sh; a.k_ss = k_ss;
+    a.q = q.p; a.k = c.k.p;
+    a.q_sb = q.sb; a.q_sh = q.sh; a.q_sw = q.ss;
+    a.k_sb = c.k.sb; a.k_sh = c.k.sh; a.k_ss = c.k.ss;
     a.B = (uint32_t)B; a.Hq = (uint32_t)Hq; a.Hkv = (uint32_t)Hkv; a.G = (uint32_t)(Hq / Hkv);
     a.S = (uint32_t)S; a.W = (uint32_t)W; a.D = (uint32_t)D;
     a.Wp = snapkv_wp(a.W); a.rblk = 0;
@@ -472,9 +463,7 @@ int snapkv_score_impl(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_sw, c
             // head sizes beyond ~250 (Gemma's 256): raise the kernels' dynamic-LDS limit (a CU has 160 KiB) -- round 6: D = 256 used to be
             // refused although the header promises D <= 1024 (the 64-key sub-tile of float32 K rows is what grows with D)
             const void* fns[2] = {nullptr, nullptr};
-            if (dtype == KVP_F32) { fns[0] = (const void*)snapkv_p1_generic<KVP_F32>; fns[1] = (const void*)snapkv_p2_generic<KVP_F32>; }
-            else if (dtype == KVP_F16) { fns[0] = (const void*)snapkv_p1_generic<KVP_F16>; fns[1] = (const void*)snapkv_p2_generic<KVP_F16>; }
-            else { fns[0] = (const void*)snapkv_p1_generic<KVP_BF16>; fns[1] = (const void*)snapkv_p2_generic<KVP_BF16>; }
+            KVP_DISPATCH_DTYPE(dtype, fns[0] = (const void*)snapkv_p1_generic<DT>; fns[1] = (const void*)snapkv_p2_generic<DT>);
             for (int i = 0; i < 2; ++i)
                 if (hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(lds1, lds2)) != hipSuccess) {
                     kvp_set_error("snapkv: cannot raise the dynamic LDS limit to %zu bytes (D=%ld, W=%ld)", std::max(lds1, lds2), (long)D, (long)W);
@@ -488,129 +477,109 @@ int snapkv_score_impl(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_sw, c
     KVP_LAUNCH("snapkv_p1_generic", stream, snapkv_p1_generic<DT><<<g1, SK_THREADS, lds1, stream>>>(a, nchunk, w.part_m, w.part_z));               \
     KVP_LAUNCH("softmax_combine_kernel", stream, softmax_combine_kernel<<<(nrows + 3) / 4, 256, 0, stream>>>(w.part_m, w.part_z, nrows, nchunk, w.rowstat, (uint32_t)W, norm_base)); \
     KVP_LAUNCH("snapkv_p2_generic", stream, snapkv_p2_generic<DT><<<g2, SK_THREADS, lds2, stream>>>(a, w.rowstat, w.colsum));
-        if (dtype == KVP_F32) { KVP_SK_GENERIC(KVP_F32) }
-        else if (dtype == KVP_F16) { KVP_SK_GENERIC(KVP_F16) }
-        else { KVP_SK_GENERIC(KVP_BF16) }
+        KVP_DISPATCH_DTYPE(dtype, KVP_SK_GENERIC(DT));
 #undef KVP_SK_GENERIC
     }
     KVP_CHECK_LAUNCH("snapkv(p1/p2)");
-    return finish_scores(w, B, Hq, Hkv, S, W, kernel_size, scores, stream, hist1, finish);
+    return finish_scores(w, c);
 }
+
+}  // namespace
+
+extern "C" size_t kvp_snapkv_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int64_t D) {
+    if (B < 1 || Hq < 1 || Hkv < 1 || S < 1 || W < 1 || D < 1) return 256;
+    return carve_snap_ws(nullptr, B, Hq, Hkv, S, W, D).total_bytes;
+}
+
+float* snapkv_ws_colsum(void* ws, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int64_t D) {
+    return carve_snap_ws(ws, B, Hq, Hkv, S, W, D).colsum;
+}
+float snapkv_pool_scale(int64_t Hq, int64_t Hkv, int64_t W, int kernel_size) {
+    return (float)(1.0 / ((double)(Hq / Hkv) * (double)W * (double)kernel_size));
+}
+
+int snapkv_score_rope_impl(const SnapCall& c, KvpRows q, const SnapRope& r) {
+    const int64_t B = c.B, Hq = c.Hq, W = c.W, D = c.D;
+    const int dtype = c.dtype;
+    hipStream_t stream = c.stream;
+    if (int rc = check_common(c)) return rc;
+    KVP_CHECK_ARG(D >= 2 && D <= 1024 && D % 2 == 0, "snapkv: RoPE needs an even head_dim (got %ld)", (long)D);
+    KVP_CHECK_ARG(q.p && r.cosp && r.sinp && c.k.p && c.scores, "snapkv: null pointer");
+    KVP_CHECK_ARG(B * Hq * W * D < ((int64_t)1 << 31), "snapkv: window too large");
+    SnapWs w = carve_snap_ws(c.ws, B, Hq, c.Hkv, c.S, W, D);
+    if (int rc = kvp_check_workspace("snapkv", c.ws, c.ws_bytes, w.total_bytes)) return rc;
+    const uint32_t total = (uint32_t)(B * Hq * W * (D / 2));
+    const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((total + SK_THREADS - 1) / SK_THREADS, 2048));
+    const bool rvec = dtype != KVP_F32 && D % 16 == 0 && ((uintptr_t)q.p % 16) == 0 && ((uintptr_t)r.cosp % 16) == 0 && ((uintptr_t)r.sinp % 16) == 0 &&
+                      ((uintptr_t)w.qrot % 16) == 0 && (q.sb * 2) % 16 == 0 && (q.sh * 2) % 16 == 0 && (q.ss * 2) % 16 == 0 && (r.cs_sb * 2) % 16 == 0 && (r.cs_sw * 2) % 16 == 0;
+    const uint32_t vblocks = std::max<uint32_t>(1, std::min<uint32_t>((total / 8 + SK_THREADS - 1) / SK_THREADS, 2048));
+    // (KERNEL, grid) for one dtype; the vector kernel exists for the 2-byte dtypes only, so its ladder has two rungs
+#define KVP_SK_ROPE(KERNEL, NBLK, DT)                                                                                        \
+    KVP_LAUNCH("snapkv_rope_kernel", stream, KERNEL<DT><<<NBLK, SK_THREADS, 0, stream>>>(                                      \
+        static_cast<const Elem<DT>::T*>(q.p), q.sb, q.sh, q.ss, static_cast<const Elem<DT>::T*>(r.cosp),                       \
+        static_cast<const Elem<DT>::T*>(r.sinp), r.cs_sb, r.cs_sw, (uint32_t)B, (uint32_t)Hq, (uint32_t)W, (uint32_t)D,        \
+        static_cast<Elem<DT>::T*>(w.qrot)));
+    if (rvec && dtype == KVP_F16) { KVP_SK_ROPE(snapkv_rope_vec_kernel, vblocks, KVP_F16) }
+    else if (rvec) { KVP_SK_ROPE(snapkv_rope_vec_kernel, vblocks, KVP_BF16) }
+    else KVP_DISPATCH_DTYPE(dtype, KVP_SK_ROPE(snapkv_rope_kernel, blocks, DT));
+#undef KVP_SK_ROPE
+    KVP_CHECK_LAUNCH("snapkv(rope)");
+    return snapkv_score_impl(c, qrot_rows(w, c));
+}
+
+// window queries from the hidden states (fused q_proj + RoPE, qproj.hip), then as above
+int snapkv_score_hidden_impl(const SnapCall& c, const SnapHidden& x, const SnapRope& r) {
+    if (int rc = check_common(c)) return rc;
+    KVP_CHECK_ARG(x.p && x.wq && r.cosp && r.sinp && c.k.p && c.scores, "snapkv: null pointer");
+    if (!kvp_qproj_rope_eligible(c.dtype, c.W, c.D, x.hidden, x.p, x.sb, x.sw, x.wq, r.cosp, r.sinp, r.cs_sb, r.cs_sw)) {
+        kvp_set_error("snapkv: fused q_proj needs bf16/f16, W = 64, D = 128, hidden %% 256 == 0, 16-byte aligned rows");
+        return KVP_EUNSUPPORTED;
+    }
+    SnapWs w = carve_snap_ws(c.ws, c.B, c.Hq, c.Hkv, c.S, c.W, c.D);
+    if (int rc = kvp_check_workspace("snapkv", c.ws, c.ws_bytes, w.total_bytes)) return rc;
+    if (int rc = kvp_qproj_rope_launch(x.p, x.sb, x.sw, x.wq, r.cosp, r.sinp, r.cs_sb, r.cs_sw, c.dtype, c.B, c.Hq, x.hidden, w.qrot, c.stream)) return rc;
+    return snapkv_score_impl(c, qrot_rows(w, c));
+}
+
+// the flat arguments that every score entry shares, in the order of their prototypes
+#define KVP_SNAP_CALL(kernel_size) \
+    SnapCall { {k, k_sb, k_sh, k_ss}, dtype, B, Hq, Hkv, S, W, D, kernel_size, scores, ws, ws_bytes, static_cast<hipStream_t>(stream_) }
 
 extern "C" int kvp_snapkv_score(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_sw, const void* k, int64_t k_sb,
                                 int64_t k_sh, int64_t k_ss, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S,
                                 int64_t W, int64_t D, int kernel_size, float* scores, void* ws, size_t ws_bytes,
                                 kvp_stream_t stream_) {
-    return snapkv_score_impl(q, q_sb, q_sh, q_sw, k, k_sb, k_sh, k_ss, dtype, B, Hq, Hkv, S, W, D, kernel_size, scores, ws, ws_bytes,
-                             static_cast<hipStream_t>(stream_), nullptr);
-}
-
-int snapkv_score_rope_impl(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_sw, const void* cosp, const void* sinp,
-                           int64_t cs_sb, int64_t cs_sw, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, int dtype,
-                           int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int64_t D, int kernel_size,
-                           float* scores, void* ws, size_t ws_bytes, hipStream_t stream, uint32_t* hist1, bool count_norm, int finish) {
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "snapkv: bad dtype %d", dtype);
-    if (int rc = check_common(B, Hq, Hkv, S, W, kernel_size)) return rc;
-    KVP_CHECK_ARG(D >= 2 && D <= 1024 && D % 2 == 0, "snapkv: RoPE needs an even head_dim (got %ld)", (long)D);
-    KVP_CHECK_ARG(q && cosp && sinp && k && scores, "snapkv: null pointer");
-    KVP_CHECK_ARG(B * Hq * W * D < ((int64_t)1 << 31), "snapkv: window too large");
-    SnapWs w = carve_snap_ws(ws, B, Hq, Hkv, S, W, D);
-    if (!ws || ws_bytes < w.total_bytes) {
-        kvp_set_error("snapkv: workspace too small (%zu < %zu)", ws_bytes, w.total_bytes);
-        return KVP_EWORKSPACE;
-    }
-    const uint32_t total = (uint32_t)(B * Hq * W * (D / 2));
-    const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((total + SK_THREADS - 1) / SK_THREADS, 2048));
-#define KVP_SK_ROPE(DT)                                                                                                      \
-    KVP_LAUNCH("snapkv_rope_kernel", stream, snapkv_rope_kernel<DT><<<blocks, SK_THREADS, 0, stream>>>(                        \
-        static_cast<const Elem<DT>::T*>(q), q_sb, q_sh, q_sw, static_cast<const Elem<DT>::T*>(cosp),                          \
-        static_cast<const Elem<DT>::T*>(sinp), cs_sb, cs_sw, (uint32_t)B, (uint32_t)Hq, (uint32_t)W, (uint32_t)D,              \
-        static_cast<Elem<DT>::T*>(w.qrot)));
-    const bool rvec = dtype != KVP_F32 && D % 16 == 0 && ((uintptr_t)q % 16) == 0 && ((uintptr_t)cosp % 16) == 0 && ((uintptr_t)sinp % 16) == 0 &&
-                      ((uintptr_t)w.qrot % 16) == 0 && (q_sb * 2) % 16 == 0 && (q_sh * 2) % 16 == 0 && (q_sw * 2) % 16 == 0 && (cs_sb * 2) % 16 == 0 && (cs_sw * 2) % 16 == 0;
-    const uint32_t vblocks = std::max<uint32_t>(1, std::min<uint32_t>((total / 8 + SK_THREADS - 1) / SK_THREADS, 2048));
-#define KVP_SK_ROPE_VEC(DT)                                                                                                  \
-    KVP_LAUNCH("snapkv_rope_kernel", stream, snapkv_rope_vec_kernel<DT><<<vblocks, SK_THREADS, 0, stream>>>(                   \
-        static_cast<const Elem<DT>::T*>(q), q_sb, q_sh, q_sw, static_cast<const Elem<DT>::T*>(cosp),                          \
-        static_cast<const Elem<DT>::T*>(sinp), cs_sb, cs_sw, (uint32_t)B, (uint32_t)Hq, (uint32_t)W, (uint32_t)D,              \
-        static_cast<Elem<DT>::T*>(w.qrot)));
-    if (rvec && dtype == KVP_F16) { KVP_SK_ROPE_VEC(KVP_F16) }
-    else if (rvec) { KVP_SK_ROPE_VEC(KVP_BF16) }
-    else if (dtype == KVP_F32) { KVP_SK_ROPE(KVP_F32) }
-    else if (dtype == KVP_F16) { KVP_SK_ROPE(KVP_F16) }
-    else { KVP_SK_ROPE(KVP_BF16) }
-#undef KVP_SK_ROPE_VEC
-#undef KVP_SK_ROPE
-    KVP_CHECK_LAUNCH("snapkv(rope)");
-    return snapkv_score_impl(w.qrot, Hq * W * D, W * D, D, k, k_sb, k_sh, k_ss, dtype, B, Hq, Hkv, S, W, D, kernel_size, scores, ws,
-                             ws_bytes, stream, hist1, count_norm, finish);
-}
-
-// window queries from the hidden states (fused q_proj + RoPE, qproj.hip), then as above
-bool kvp_qproj_rope_eligible(int dtype, int64_t W, int64_t D, int64_t K, const void* x, int64_t x_sb, int64_t x_sw, const void* w,
-                             const void* cosp, const void* sinp, int64_t cs_sb, int64_t cs_sw);
-int kvp_qproj_rope_launch(const void* x, int64_t x_sb, int64_t x_sw, const void* w, const void* cosp, const void* sinp, int64_t cs_sb,
-                          int64_t cs_sw, int dtype, int64_t B, int64_t Hq, int64_t K, void* out, hipStream_t stream);
-
-int snapkv_score_hidden_impl(const void* hidden_win, int64_t x_sb, int64_t x_sw, const void* wq, int64_t hidden, const void* cosp,
-                             const void* sinp, int64_t cs_sb, int64_t cs_sw, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss,
-                             int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int64_t D, int kernel_size,
-                             float* scores, void* ws, size_t ws_bytes, hipStream_t stream, uint32_t* hist1, int finish) {
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "snapkv: bad dtype %d", dtype);
-    if (int rc = check_common(B, Hq, Hkv, S, W, kernel_size)) return rc;
-    KVP_CHECK_ARG(hidden_win && wq && cosp && sinp && k && scores, "snapkv: null pointer");
-    if (!kvp_qproj_rope_eligible(dtype, W, D, hidden, hidden_win, x_sb, x_sw, wq, cosp, sinp, cs_sb, cs_sw)) {
-        kvp_set_error("snapkv: fused q_proj needs bf16/f16, W = 64, D = 128, hidden %% 256 == 0, 16-byte aligned rows");
-        return KVP_EUNSUPPORTED;
-    }
-    SnapWs w = carve_snap_ws(ws, B, Hq, Hkv, S, W, D);
-    if (!ws || ws_bytes < w.total_bytes) {
-        kvp_set_error("snapkv: workspace too small (%zu < %zu)", ws_bytes, w.total_bytes);
-        return KVP_EWORKSPACE;
-    }
-    if (int rc = kvp_qproj_rope_launch(hidden_win, x_sb, x_sw, wq, cosp, sinp, cs_sb, cs_sw, dtype, B, Hq, hidden, w.qrot, stream)) return rc;
-    return snapkv_score_impl(w.qrot, Hq * W * D, W * D, D, k, k_sb, k_sh, k_ss, dtype, B, Hq, Hkv, S, W, D, kernel_size, scores, ws,
-                             ws_bytes, stream, hist1, false, finish);
+    return snapkv_score_impl(KVP_SNAP_CALL(kernel_size), {q, q_sb, q_sh, q_sw});
 }
 
 extern "C" int kvp_snapkv_score_hidden(const void* hidden_win, int64_t x_sb, int64_t x_sw, const void* wq, int64_t hidden,
                                        const void* cosp, const void* sinp, int64_t cs_sb, int64_t cs_sw, const void* k, int64_t k_sb,
                                        int64_t k_sh, int64_t k_ss, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W,
                                        int64_t D, int kernel_size, float* scores, void* ws, size_t ws_bytes, kvp_stream_t stream_) {
-    return snapkv_score_hidden_impl(hidden_win, x_sb, x_sw, wq, hidden, cosp, sinp, cs_sb, cs_sw, k, k_sb, k_sh, k_ss, dtype, B, Hq, Hkv,
-                                    S, W, D, kernel_size, scores, ws, ws_bytes, static_cast<hipStream_t>(stream_), nullptr, SNAP_FINISH_FULL);
+    return snapkv_score_hidden_impl(KVP_SNAP_CALL(kernel_size), {hidden_win, x_sb, x_sw, wq, hidden}, {cosp, sinp, cs_sb, cs_sw});
 }
 
 extern "C" int kvp_snapkv_score_rope(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_sw, const void* cosp, const void* sinp,
                                      int64_t cs_sb, int64_t cs_sw, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, int dtype,
                                      int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int64_t D, int kernel_size,
                                      float* scores, void* ws, size_t ws_bytes, kvp_stream_t stream_) {
-    return snapkv_score_rope_impl(q, q_sb, q_sh, q_sw, cosp, sinp, cs_sb, cs_sw, k, k_sb, k_sh, k_ss, dtype, B, Hq, Hkv, S, W, D,
-                                  kernel_size, scores, ws, ws_bytes, static_cast<hipStream_t>(stream_), nullptr, false);
+    return snapkv_score_rope_impl(KVP_SNAP_CALL(kernel_size), {q, q_sb, q_sh, q_sw}, {cosp, sinp, cs_sb, cs_sw});
 }
 
 extern "C" int kvp_snapkv_score_from_attn(const void* attn, int64_t a_sb, int64_t a_sh, int64_t a_sw, int dtype, int64_t B,
                                           int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int kernel_size, float* scores,
                                           void* ws, size_t ws_bytes, kvp_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    KVP_CHECK_ARG(dtype == KVP_F32 || dtype == KVP_F16 || dtype == KVP_BF16, "snapkv: bad dtype %d", dtype);
-    if (int rc = check_common(B, Hq, Hkv, S, W, kernel_size)) return rc;
+    const SnapCall c{{nullptr, 0, 0, 0}, dtype, B, Hq, Hkv, S, W, 1, kernel_size, scores, ws, ws_bytes, static_cast<hipStream_t>(stream_)};
+    hipStream_t stream = c.stream;
+    if (int rc = check_common(c)) return rc;
     KVP_CHECK_ARG(attn && scores, "snapkv: null pointer");
     SnapWs w = carve_snap_ws(ws, B, Hq, Hkv, S, W, 1);
-    if (!ws || ws_bytes < w.total_bytes) {
-        kvp_set_error("snapkv: workspace too small (%zu < %zu)", ws_bytes, w.total_bytes);
-        return KVP_EWORKSPACE;
-    }
+    if (int rc = kvp_check_workspace("snapkv", ws, ws_bytes, w.total_bytes)) return rc;
     const uint64_t total = (uint64_t)B * Hkv * (S - W);
     const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((total + SK_THREADS - 1) / SK_THREADS, 4096));
-#define KVP_SK_ATTN(DT) \
-    KVP_LAUNCH("snapkv_colsum_from_attn", stream, snapkv_colsum_from_attn<DT><<<blocks, SK_THREADS, 0, stream>>>(static_cast<const Elem<DT>::T*>(attn), a_sb, a_sh, a_sw, (uint32_t)B, (uint32_t)Hq, (uint32_t)Hkv, (uint32_t)(S - W), (uint32_t)W, w.colsum));
-    if (dtype == KVP_F32) { KVP_SK_ATTN(KVP_F32) }
-    else if (dtype == KVP_F16) { KVP_SK_ATTN(KVP_F16) }
-    else { KVP_SK_ATTN(KVP_BF16) }
-#undef KVP_SK_ATTN
+    KVP_DISPATCH_DTYPE(dtype, KVP_LAUNCH("snapkv_colsum_from_attn", stream, snapkv_colsum_from_attn<DT><<<blocks, SK_THREADS, 0, stream>>>(static_cast<const Elem<DT>::T*>(attn), a_sb, a_sh, a_sw, (uint32_t)B, (uint32_t)Hq, (uint32_t)Hkv, (uint32_t)(S - W), (uint32_t)W, w.colsum)));
     KVP_CHECK_LAUNCH("snapkv(from_attn)");
-    return finish_scores(w, B, Hq, Hkv, S, W, kernel_size, scores, stream);
+    return finish_scores(w, c);
 }
 
 // FINCH scores (finch_press.py:56-83): the window attention of kvp_snapkv_score_rope for an arbitrary window (the
@@ -619,6 +588,7 @@ extern "C" int kvp_finch_score(const void* q, int64_t q_sb, int64_t q_sh, int64_
                                int64_t cs_sb, int64_t cs_sw, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, int dtype,
                                int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int64_t D, int normalize_scores,
                                float* scores, void* ws, size_t ws_bytes, kvp_stream_t stream_) {
-    return snapkv_score_rope_impl(q, q_sb, q_sh, q_sw, cosp, sinp, cs_sb, cs_sw, k, k_sb, k_sh, k_ss, dtype, B, Hq, Hkv, S, W, D,
-                                  1, scores, ws, ws_bytes, static_cast<hipStream_t>(stream_), nullptr, normalize_scores != 0);
+    SnapCall c = KVP_SNAP_CALL(1);
+    c.count_norm = normalize_scores != 0;
+    return snapkv_score_rope_impl(c, {q, q_sb, q_sh, q_sw}, {cosp, sinp, cs_sb, cs_sw});
 }

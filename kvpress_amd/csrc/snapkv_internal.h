@@ -45,14 +45,22 @@ enum { SNAP_FINISH_FULL = 0,    // pool + scale into `scores`, pad columns = max
 float* snapkv_ws_colsum(void* ws, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int64_t D);
 float snapkv_pool_scale(int64_t Hq, int64_t Hkv, int64_t W, int kernel_size);  // 1 / (G * W * kernel_size)
 
-// Score entry points with an optional fused first top-k histogram (hist1 [B*Hkv][4096] over the S - W non-pad columns;
-// the pad columns of `scores` are then left unwritten).  finish: what happens after the two attention passes.  Defined in snapkv.hip, used by the fused compress (compress.hip).
-int snapkv_score_rope_impl(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_sw, const void* cosp, const void* sinp,
-                           int64_t cs_sb, int64_t cs_sw, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, int dtype,
-                           int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int64_t D, int kernel_size,
-                           float* scores, void* ws, size_t ws_bytes, hipStream_t stream, uint32_t* hist1, bool count_norm = false,
-                           int finish = 0);
-int snapkv_score_hidden_impl(const void* hidden_win, int64_t x_sb, int64_t x_sw, const void* wq, int64_t hidden, const void* cosp,
-                             const void* sinp, int64_t cs_sb, int64_t cs_sw, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss,
-                             int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int64_t D, int kernel_size,
-                             float* scores, void* ws, size_t ws_bytes, hipStream_t stream, uint32_t* hist1, int finish = 0);
+// One SnapKV scoring call on the host side (the kernels get SnapArgs).  The three scorers below differ in where the window queries come from, nothing else.
+struct SnapCall {
+    KvpRows k;   // keys [B,Hkv,S,D]
+    int dtype;
+    int64_t B, Hq, Hkv, S, W, D;
+    int kernel_size;
+    float* scores;   // [B,Hkv,S]
+    void* ws;        // kvp_snapkv_workspace_bytes
+    size_t ws_bytes;
+    hipStream_t stream;
+    uint32_t* hist1 = nullptr;      // fused compress: also the select's first histogram [B*Hkv][4096] over the S - W non-pad columns (the pad columns of `scores` are then left unwritten)
+    bool count_norm = false;        // FINCH: window row w weighted by its S - W + w visible keys
+    int finish = SNAP_FINISH_FULL;  // what happens after the two attention passes
+};
+struct SnapRope { const void *cosp, *sinp; int64_t cs_sb, cs_sw; };                        // the window's rotary tables [1 or B, W, D]
+struct SnapHidden { const void* p; int64_t sb, sw; const void* wq; int64_t hidden; };      // hidden states of the window [B, W, hidden] + q_proj.weight
+// Defined in snapkv.hip, used by the fused compress (compress.hip).  q: PRE-RoPE window queries [B,Hq,W,D]
+int snapkv_score_rope_impl(const SnapCall& c, KvpRows q, const SnapRope& r);
+int snapkv_score_hidden_impl(const SnapCall& c, const SnapHidden& x, const SnapRope& r);

@@ -582,10 +582,7 @@ int topk_select_impl(const float* scores, int64_t R, int64_t S, int64_t row_stri
         KVP_CHECK_LAUNCH("topk(row)");
         return KVP_OK;
     }
-    if (!ws || ws_bytes < w.total_bytes) {
-        kvp_set_error("topk: workspace too small (%zu < %zu)", ws_bytes, w.total_bytes);
-        return KVP_EWORKSPACE;
-    }
+    if (int rc = kvp_check_workspace("topk", ws, ws_bytes, w.total_bytes)) return rc;
     if (!ws_clean) {
         KVP_CHECK_ARG(!hist1_ready, "topk: a fused first pass needs a clean workspace");
         if (hipMemsetAsync(ws, 0, w.zero_bytes, stream) != hipSuccess) {

@@ -365,10 +365,7 @@ int topk_order_by_score(const float* scores, int64_t R, int64_t S, int64_t row_s
     if (R == 0 || k == 0) return KVP_OK;
     KVP_CHECK_ARG(R <= 65535 && k < ((int64_t)1 << 30) && S < ((int64_t)1 << 31), "topk(order): shape too large (R=%ld k=%ld)", (long)R, (long)k);
     const OrderPlan p = order_plan(R, k);
-    if (!ws || ws_bytes < p.total_bytes) {
-        kvp_set_error("topk(order): workspace too small (%zu < %zu)", ws_bytes, p.total_bytes);
-        return KVP_EWORKSPACE;
-    }
+    if (int rc = kvp_check_workspace("topk(order)", ws, ws_bytes, p.total_bytes)) return rc;
     OrderArgs a;
     a.scores = scores; a.row_stride = row_stride; a.idx = idx;
     a.S = (uint32_t)S; a.k = (uint32_t)k; a.kmask = smallest ? 0xFFFFFFFFu : 0u; a.ntiles = p.ntiles;

@@ -77,6 +77,69 @@ def test_product_library_exports_no_contrib_kernels():
     assert not [l for l in out.splitlines() if any(t in l for t in ("lagkv", "think", "observed_attention", "zero_channels"))]
 
 
+def _exported(path):
+    import subprocess
+
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return sorted(line.split()[-1] for line in out.splitlines() if line.strip())
+
+
+def internal_api():
+    """the C++ functions kvp_host.h marks KVP_INTERNAL_API (what csrc/contrib/*.hip link against in the product library)"""
+    text = open(os.path.join(ROOT, "kvpress_amd", "csrc", "kvp_host.h")).read()
+    return sorted(set(re.findall(r"^KVP_INTERNAL_API\s[^;(]*?\b(\w+)\s*\(", text, flags=re.M)))
+
+
+# Kernel handles the toolchain emits (weak, default visibility) for the one kernel template with external linkage, snapkv_p2_asm in
+# snapkv_mfma.hip; every other kernel sits in an anonymous namespace.  By exact name.
+TOOLCHAIN_SYMBOLS = {"_Z13snapkv_p2_asmILi1EEv8SnapArgsjPKfPfS3_PKj", "_Z13snapkv_p2_asmILi2EEv8SnapArgsjPKfPfS3_PKj"}
+# hipcc's one-byte marker per translation unit: the 16 hex digits are a hash over the source PATH and the options, so they differ from
+# checkout to checkout and cannot be listed by exact name -- the full form is matched instead, nothing looser
+HIP_CUID = re.compile(r"__hip_cuid_[0-9a-f]{1,16}")
+
+
+def test_libraries_export_only_what_the_headers_declare(lib):
+    """the converse of test_header_symbols_exported: the libraries are built with -fvisibility=hidden, so their dynamic symbol tables
+    hold the extern "C" entries of their headers, the KVP_INTERNAL_API functions of kvp_host.h (product library only), and nothing else"""
+    from kvpress_amd import _native
+
+    internal = internal_api()
+    assert internal and all(n.startswith("kvp_") for n in internal)
+    for path, headers, allowed_cxx in ((_native.LIB_PATH, ("kvpress_hip.h", "kvpress_hip_lab.h"), internal),
+                                       (_native.CONTRIB_LIB_PATH, ("kvpress_hip_extra.h",), [])):
+        declared = set(declared_symbols(headers))
+        mangled_ok = tuple(f"_Z{len(n)}{n}" for n in allowed_cxx)
+        stray = []
+        for s in _exported(path):
+            if s in declared or s in TOOLCHAIN_SYMBOLS or HIP_CUID.fullmatch(s):
+                continue
+            if mangled_ok and s.startswith(mangled_ok):   # (the length prefix of the mangling makes this the exact function name)
+                continue
+            stray.append(s)
+        assert not stray, f"{os.path.basename(path)} exports symbols outside its headers: {stray}"
+
+
+def test_no_hand_written_prototypes_of_other_files_functions():
+    """a function that one .hip defines and another calls is declared in a header (kvp_host.h or its family's *_internal.h), never by a
+    body-less prototype typed again in the calling .hip"""
+    csrc = os.path.join(ROOT, "kvpress_amd", "csrc")
+    files = [os.path.join(d, f) for d, _, fs in os.walk(csrc) for f in fs if f.endswith(".hip")]
+    assert len(files) >= 20
+    # a declarator at column 0: specifiers / return type, name, balanced parameter list, then `;` (prototype) or `{` (definition)
+    pat = re.compile(r'^(?![ \t#/}])(?:[\w:<>*&"]+[ \t]+)+[*&]?(\w+)\((?:[^;{}()]|\([^()]*\))*\)\s*(;|\{)', flags=re.M)
+    defined, protos = {}, []
+    for f in files:
+        text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", open(f).read(), flags=re.S))
+        for m in pat.finditer(text):
+            if m.group(2) == "{":
+                defined.setdefault(m.group(1), set()).add(f)
+            else:
+                protos.append((f, m.group(1)))
+    assert "kvp_rownorm_launch" in defined and "kvp_gather_kv" in defined     # the pattern sees the functions this is about
+    bad = [(os.path.basename(f), n) for f, n in protos if defined.get(n, set()) - {f}]
+    assert not bad, f"prototypes of functions defined in another .hip (declare them in kvp_host.h): {bad}"
+
+
 def test_binding_covers_header(lib):
     from kvpress_amd import _native
 
