@@ -20,13 +20,18 @@ LIB_PATH = os.environ.get("KVPRESS_HIP_LIB") or os.path.join(_HERE, "lib", "libk
 CONTRIB_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libkvpress_hip_contrib.so")
 
 KVP_F32, KVP_F16, KVP_BF16 = 0, 1, 2
+KVP_EASYNC = -5
 ORDER_POSITION, ORDER_SCORE = 0, 1
-TOPK_WS_CLEAN = 0x100
-_TOPK_WS: dict = {}  # (thread, device index, stream, R, S) -> zero-initialised, self-cleaning workspace
-_TOPK_WS_LOCK = threading.Lock()
+TOPK_WS_CLEAN, TOPK_SMALLEST = 0x100, 0x200
+CUR_LEVERAGE = {"key": 0, "value": 1, "kv_avg": 2, "kv_product": 3}
 _DTYPES = {torch.float32: KVP_F32, torch.float16: KVP_F16, torch.bfloat16: KVP_BF16}
+_TOPK_WS: dict = {}   # (thread, kind of use, device index, stream, call shape...) -> zero-initialised, self-cleaning workspace (_clean_ws)
+_TOPK_WS_LOCK = threading.Lock()
+_WS_BYTES: dict = {}  # (kvp_*_workspace_bytes, shape...) -> its answer (_ws_bytes)
 
-# name -> (restype, argtypes); mirrors include/kvpress_hip.h line by line
+# ---- loading and the signature tables -----------------------------------------------------------------------------------------------
+# name -> (restype, argtypes); mirrors include/kvpress_hip.h line by line (tests/test_capi_symbols.py::test_binding_covers_header holds
+# every entry against its prototype: return type, arity, order and type of the parameters)
 _I64 = c_int64
 SIGNATURES = {
     "kvp_version": (c_int, []),
@@ -153,9 +158,7 @@ def contrib_lib() -> ctypes.CDLL:
     return _contrib_lib
 
 
-KVP_EASYNC = -5
-
-
+# ---- marshalling and workspace helpers ------------------------------------------------------------------------------------------------
 def _check(rc: int, what: str):
     if rc != 0:
         msg = lib().kvp_last_error()
@@ -167,11 +170,22 @@ def _check(rc: int, what: str):
         raise KvpressHipError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
 
 
+def _call(name: str, *args, contrib: bool = False, what: Optional[str] = None, clean_ws: Optional[torch.Tensor] = None):
+    """Call the entry point ``name`` of the library (``contrib``: of the contrib library); a non-zero return code raises KvpressHipError under that same name (``what``:
+    under another).  ``clean_ws`` is the cached self-cleaning workspace the call used: a failed call may leave dirty histograms
+    behind, so it leaves the cache before the error is raised and is never reused as "clean"."""
+    rc = getattr(contrib_lib() if contrib else lib(), name)(*args)
+    if rc != 0:
+        if clean_ws is not None:
+            _drop_ws(clean_ws)
+        _check(rc, what or name)
+
+
 def async_error_check() -> None:
     """Raise KvpressHipError if a kernel has reported an asynchronous failure since the last check (no synchronisation: call it
     after a stream sync to cover everything enqueued so far).  No-op when the library has not been loaded."""
     if _lib is not None:
-        _check(_lib.kvp_async_error_check(), "kvp_async_error_check")
+        _call("kvp_async_error_check")
 
 
 def _dev(t: torch.Tensor):
@@ -183,14 +197,67 @@ def _dev(t: torch.Tensor):
     return t
 
 
-def _rows_last_contig(t: torch.Tensor) -> torch.Tensor:
-    """[..., D] view whose last dim is contiguous (sliced cache views pass through untouched)."""
+def _rows(t: torch.Tensor) -> torch.Tensor:
+    """_dev + a [..., D] view whose last dim is contiguous (sliced cache views pass through untouched)."""
+    if not t.is_cuda or t.dtype not in _DTYPES:
+        _dev(t)   # raises
     return t if (t.shape[-1] == 1 or t.stride(-1) == 1) else t.contiguous()
 
 
-def _st(t: torch.Tensor, i: int) -> int:
-    """Element stride of dim i; 0 for size-1 dims (torch reports arbitrary strides there)."""
-    return 0 if t.shape[i] == 1 else t.stride(i)
+def _p(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None   # (ints / None: ctypes converts them for a c_void_p parameter)
+
+
+def _tensor(t: torch.Tensor, n: int = 3) -> tuple:
+    """The argument group of a tensor: its pointer and the element strides of its first ``n`` dims; 0 for size-1 dims (torch reports
+    arbitrary strides there)."""
+    shape, stride = t.shape, t.stride()
+    if n == 3:   # (spelled out: a third of the cost of the general form, on every call of the decode regime)
+        return (t.data_ptr(), 0 if shape[0] == 1 else stride[0], 0 if shape[1] == 1 else stride[1], 0 if shape[2] == 1 else stride[2])
+    return (t.data_ptr(), *[0 if shape[i] == 1 else stride[i] for i in range(n)])
+
+
+def _kv(keys: torch.Tensor, values: torch.Tensor, same: bool = True):
+    """The keys / values prelude: both on a device in a supported dtype with a contiguous last dim and (``same``) of one dtype and
+    shape.  Returns them and B, H, S, D of the keys."""
+    keys, values = _rows(keys), _rows(values)
+    if same:
+        assert keys.dtype == values.dtype and keys.shape == values.shape
+    return (keys, values, *keys.shape)
+
+
+def _queries(q: torch.Tensor, keys: torch.Tensor):
+    """Window queries [B,Hq,W,D] for prepared keys [B,Hkv,S,D]: in the keys' dtype, last dim contiguous.  Returns them and
+    B, Hq, Hkv, S, W, D."""
+    q = _rows(q)
+    if q.dtype != keys.dtype:
+        q = q.to(keys.dtype)
+    B, Hq, W, D = q.shape
+    Bk, Hkv, S, Dk = keys.shape
+    assert B == Bk and D == Dk and Hq % Hkv == 0, (q.shape, keys.shape)
+    return q, B, Hq, Hkv, S, W, D
+
+
+def _rotary(cos: torch.Tensor, sin: torch.Tensor, dt: torch.dtype, window: Optional[tuple] = None):
+    """The rotary tables as the library takes them: dtype ``dt``, contiguous last dim, equal strides.  With ``window = (B, W, D)`` they
+    are the window's, [1 or B, W, D], and a table with ONE row is broadcast over the window (stride 0), which is what the
+    reference's ``cos[:, -W:].unsqueeze(1)`` does when a decoding step hands over the current position only (DecodingPress with a
+    window scorer)."""
+    cos, sin = _rows(cos.to(dt)), _rows(sin.to(dt))
+    if window is not None:
+        B, W, D = window
+        assert cos.shape == sin.shape and cos.shape[-1] == D and cos.shape[0] in (1, B) and cos.shape[-2] in (1, W), (cos.shape, (B, W, D))
+    if sin.stride() != cos.stride():
+        sin, cos = sin.contiguous(), cos.contiguous()
+    if window is not None and cos.shape[-2] == 1 and W > 1:
+        cos, sin = cos.expand(-1, W, -1), sin.expand(-1, W, -1)
+    return cos, sin
+
+
+def _tables(cos: torch.Tensor, sin: torch.Tensor) -> tuple:
+    """The argument group of _rotary's tables: both pointers and their common strides."""
+    shape, stride = cos.shape, cos.stride()
+    return (cos.data_ptr(), sin.data_ptr(), 0 if shape[0] == 1 else stride[0], 0 if shape[1] == 1 else stride[1])
 
 
 def _stream(t: torch.Tensor):
@@ -219,82 +286,71 @@ def _ws(nbytes: int, like: torch.Tensor) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=like.device)
 
 
-def _p(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None else None   # (ints / None: ctypes converts them for a c_void_p parameter)
+def _scratch(name: str, like: torch.Tensor, *shape, contrib: bool = False) -> torch.Tensor:
+    """A fresh scratch workspace of ``name(*shape)`` bytes (``name``: the *_workspace_bytes companion of the entry) on like's device."""
+    return _ws(getattr(contrib_lib() if contrib else lib(), name)(*shape), like)
 
 
-# ------------------------------------------------------------------------------------------------
+def _ws_bytes(fn_name: str, *shape) -> int:
+    """kvp_*_workspace_bytes(shape), remembered per shape (a ctypes call per compress is measurable in the decode regime)."""
+    key = (fn_name,) + shape
+    n = _WS_BYTES.get(key)
+    if n is None:
+        if len(_WS_BYTES) > 256:
+            _WS_BYTES.clear()
+        n = _WS_BYTES[key] = int(getattr(lib(), fn_name)(*shape))
+    return n
+
+
+def _clean_ws(kind: str, shape: tuple, nbytes: int, device, stream_handle: int) -> torch.Tensor:
+    """The zero-filled-once workspace of a select or a fused compress, one per (calling thread, kind of use, device, stream, call
+    shape): the calls leave its histogram region clean, so it is passed with KVP_TOPK_WS_CLEAN from then on.  Two Python threads
+    never share one, even on the same stream."""
+    key = (threading.get_ident(), kind, device.index, stream_handle) + shape
+    with _TOPK_WS_LOCK:
+        ws = _TOPK_WS.get(key)
+        if ws is None:
+            if len(_TOPK_WS) > 64:
+                _TOPK_WS.clear()
+            ws = torch.zeros(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+            _TOPK_WS[key] = ws
+    return ws
+
+
+def _drop_ws(ws: torch.Tensor):
+    with _TOPK_WS_LOCK:
+        for key in [k for k, v in _TOPK_WS.items() if v is ws]:
+            del _TOPK_WS[key]
+
+
+def _fused_compress(name: str, kind: str, shape: tuple, keys: torch.Tensor, Hkv: int, n: int, order: int, run: bool, *args):
+    """The second half of the fused compress wrappers: (K', V') [B,Hkv,n,D] in the keys' dtype, the clean workspace of ``shape`` (which
+    is also what kvp_<kind>_compress_workspace_bytes takes), then ``name(*args, n, K', V', workspace, flags, stream)`` if ``run``."""
+    ko = torch.empty((keys.shape[0], Hkv, n, keys.shape[3]), dtype=keys.dtype, device=keys.device)
+    vo = torch.empty_like(ko)
+    if run:
+        with _on_device(keys.device):
+            st = _stream(keys)
+            ws = _clean_ws(kind, shape, _ws_bytes("kvp_" + kind + "_compress_workspace_bytes", *shape), keys.device, st)
+            _call(name, *args, n, _p(ko), _p(vo), _p(ws), ws.numel(), TOPK_WS_CLEAN | (int(order) & ORDER_SCORE), st, clean_ws=ws)
+    return ko, vo
+
+
+# ---- product wrappers, in the order of include/kvpress_hip.h --------------------------------------------------------------------------
 def rownorm_score(x: torch.Tensor, scale: float) -> torch.Tensor:
     """out[b,h,s] = scale * ||x[b,h,s,:]||_2, float32 [B,H,S]."""
-    x = _rows_last_contig(_dev(x))
+    x = _rows(x)
     B, H, S, D = x.shape
+    ptr, *strides = _tensor(x)
     out = torch.empty((B, H, S), dtype=torch.float32, device=x.device)
     with _on_device(x.device):
-        _check(lib().kvp_rownorm_score(_p(x), _DTYPES[x.dtype], B, H, S, D, _st(x, 0), _st(x, 1), _st(x, 2),
-                                       float(scale), _p(out), _stream(x)), "kvp_rownorm_score")
+        _call("kvp_rownorm_score", ptr, _DTYPES[x.dtype], B, H, S, D, *strides, float(scale), _p(out), _stream(x))
     return out
-
-
-def observed_attention_score(attentions: torch.Tensor, num_kv_heads: int) -> torch.Tensor:
-    """Average attention weight every key receives (observed_attention_press.py:42-48): attentions [B,Hq,Sq,S] -> [B,Hkv,S] float32."""
-    a = _rows_last_contig(_dev(attentions))
-    B, Hq, Sq, S = a.shape
-    assert Hq % num_kv_heads == 0, (a.shape, num_kv_heads)
-    out = torch.empty((B, num_kv_heads, S), dtype=torch.float32, device=a.device)
-    with _on_device(a.device):
-        _check(contrib_lib().kvp_observed_attention_score(_p(a), _st(a, 0), _st(a, 1), _st(a, 2), _DTYPES[a.dtype], B, Hq, num_kv_heads, Sq, S,
-                                                  _p(out), _stream(a)), "kvp_observed_attention_score")
-    return out
-
-
-def lagkv_score(keys: torch.Tensor, values: torch.Tensor, n_sink: int, lag_size: int, cross_scoring: bool) -> torch.Tensor:
-    """LagKV scores [B,H,S] float32 (lagkv_press.py:56-97) for S >= n_sink + 2 * lag_size."""
-    keys = _rows_last_contig(_dev(keys))
-    values = _rows_last_contig(_dev(values))
-    assert keys.dtype == values.dtype and keys.shape == values.shape
-    B, H, S, D = keys.shape
-    out = torch.empty((B, H, S), dtype=torch.float32, device=keys.device)
-    with _on_device(keys.device):
-        _check(contrib_lib().kvp_lagkv_score(_p(keys), _st(keys, 0), _st(keys, 1), _st(keys, 2), _p(values), _st(values, 0), _st(values, 1),
-                                     _st(values, 2), _DTYPES[keys.dtype], B, H, S, D, int(n_sink), int(lag_size), int(bool(cross_scoring)),
-                                     _p(out), _stream(keys)), "kvp_lagkv_score")
-    return out
-
-
-def think_channel_scores(q_win: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
-    """ThinK's per-channel scores [B,Hkv,D] float32 (think_press.py:72-76) from the RoPE'd window queries [B,Hq,W,D] and keys."""
-    keys = _rows_last_contig(_dev(keys))
-    q_win = _rows_last_contig(_dev(q_win))
-    if q_win.dtype != keys.dtype:
-        q_win = q_win.to(keys.dtype)
-    B, Hq, W, D = q_win.shape
-    Bk, Hkv, S, Dk = keys.shape
-    assert B == Bk and D == Dk and Hq % Hkv == 0, (q_win.shape, keys.shape)
-    out = torch.empty((B, Hkv, D), dtype=torch.float32, device=keys.device)
-    with _on_device(keys.device):
-        nws = contrib_lib().kvp_think_workspace_bytes(B, Hkv, S, D)
-        ws = _ws(nws, keys)
-        _check(contrib_lib().kvp_think_channel_scores(_p(q_win), _st(q_win, 0), _st(q_win, 1), _st(q_win, 2), _p(keys), _st(keys, 0), _st(keys, 1),
-                                              _st(keys, 2), _DTYPES[keys.dtype], B, Hq, Hkv, S, W, D, _p(out), _p(ws), ws.numel(), _stream(keys)),
-               "kvp_think_channel_scores")
-    return out
-
-
-def zero_channels_(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
-    """x[b,h,:,idx[b,h,j]] = 0 in place (think_press.py:81-82); x [B,H,S,D] with a contiguous last dim, idx [B,H,n] int32."""
-    assert x.is_cuda and x.stride(-1) == 1, "zero_channels_ works in place on a device tensor with contiguous rows"
-    B, H, S, D = x.shape
-    assert idx.is_cuda and idx.device == x.device and tuple(idx.shape[:2]) == (B, H), (idx.shape, x.shape)
-    idx = idx.to(torch.int32).contiguous()
-    with _on_device(x.device):
-        _check(contrib_lib().kvp_zero_channels(_p(x), _st(x, 0), _st(x, 1), _st(x, 2), _DTYPES[x.dtype], B, H, S, D, _p(idx), idx.shape[2], _stream(x)),
-               "kvp_zero_channels")
-    return x
 
 
 def rowdot_score(x: torch.Tensor, filt: torch.Tensor, scale: float) -> torch.Tensor:
     """out[b,h,s] = scale * <x[b,h,s,:], filt[h,:]>, float32 [B,H,S]; filt [H,D] in x's dtype (qfilter_press.py:79-82)."""
-    x = _rows_last_contig(_dev(x))
+    x = _rows(x)
     B, H, S, D = x.shape
     filt = _dev(filt)
     assert tuple(filt.shape) == (H, D), (filt.shape, x.shape)
@@ -302,43 +358,242 @@ def rowdot_score(x: torch.Tensor, filt: torch.Tensor, scale: float) -> torch.Ten
         filt = filt.to(device=x.device, dtype=x.dtype)
     if filt.stride(-1) != 1:
         filt = filt.contiguous()
+    ptr, *strides = _tensor(x)
     out = torch.empty((B, H, S), dtype=torch.float32, device=x.device)
     with _on_device(x.device):
-        _check(lib().kvp_rowdot_score(_p(x), _DTYPES[x.dtype], B, H, S, D, _st(x, 0), _st(x, 1), _st(x, 2), _p(filt), _st(filt, 0),
-                                      float(scale), _p(out), _stream(x)), "kvp_rowdot_score")
+        _call("kvp_rowdot_score", ptr, _DTYPES[x.dtype], B, H, S, D, *strides, *_tensor(filt, 1), float(scale), _p(out), _stream(x))
     return out
 
 
-CUR_LEVERAGE = {"key": 0, "value": 1, "kv_avg": 2, "kv_product": 3}
-
-
-def cur_score(keys: torch.Tensor, values: torch.Tensor, leverage_type: str, local_window_size: int, num_sinks: int) -> torch.Tensor:
-    """CUR leverage scores [B,H,S] float32 (local_window_size 0 = no local approximation)."""
-    keys = _rows_last_contig(_dev(keys))
-    values = _rows_last_contig(_dev(values))
-    assert keys.dtype == values.dtype and keys.shape[:3] == values.shape[:3] and keys.shape[3] == values.shape[3]
-    if leverage_type not in CUR_LEVERAGE:
-        raise ValueError("Unknown leverage type: choose from 'kv_avg', 'key', 'value' or 'kv_product'")
-    B, H, S, D = keys.shape
-    scores = torch.empty((B, H, S), dtype=torch.float32, device=keys.device)
+def snapkv_score(q_win: torch.Tensor, keys: torch.Tensor, kernel_size: int) -> torch.Tensor:
+    """SnapKV scores [B,Hkv,S] float32 from RoPE'd window queries [B,Hq,W,D] and keys [B,Hkv,S,D]."""
+    keys = _rows(keys)
+    q_win, B, Hq, Hkv, S, W, D = _queries(q_win, keys)
+    scores = torch.empty((B, Hkv, S), dtype=torch.float32, device=keys.device)
     with _on_device(keys.device):
-        ws = _ws(lib().kvp_cur_workspace_bytes(B, H, S), keys)
-        _check(lib().kvp_cur_score(_p(keys), _st(keys, 0), _st(keys, 1), _st(keys, 2), _p(values), _st(values, 0), _st(values, 1),
-                                   _st(values, 2), _DTYPES[keys.dtype], B, H, S, D, CUR_LEVERAGE[leverage_type], int(local_window_size),
-                                   int(num_sinks), _p(scores), _p(ws), ws.numel(), _stream(keys)), "kvp_cur_score")
+        ws = _scratch("kvp_snapkv_workspace_bytes", keys, B, Hq, Hkv, S, W, D)
+        _call("kvp_snapkv_score", *_tensor(q_win), *_tensor(keys), _DTYPES[keys.dtype], B, Hq, Hkv, S, W, D, int(kernel_size),
+              _p(scores), _p(ws), ws.numel(), _stream(keys))
     return scores
+
+
+def snapkv_score_rope(q_pre: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, keys: torch.Tensor,
+                      kernel_size: int, _finch_normalize=None) -> torch.Tensor:
+    """SnapKV scores from the PRE-RoPE window queries [B,Hq,W,D] and the window's cos/sin [1 or B, W, D]:
+    the RoPE (q*cos + rotate_half(q)*sin, rounded like torch does in the model dtype) runs in the library."""
+    keys = _rows(keys)
+    q_pre, B, Hq, Hkv, S, W, D = _queries(q_pre, keys)
+    cos, sin = _rotary(cos, sin, keys.dtype, (B, W, D))
+    scores = torch.empty((B, Hkv, S), dtype=torch.float32, device=keys.device)
+    with _on_device(keys.device):
+        ws = _scratch("kvp_snapkv_workspace_bytes", keys, B, Hq, Hkv, S, W, D)
+        name, last = (("kvp_snapkv_score_rope", int(kernel_size)) if _finch_normalize is None
+                      else ("kvp_finch_score", int(_finch_normalize)))
+        _call(name, *_tensor(q_pre), *_tables(cos, sin), *_tensor(keys), _DTYPES[keys.dtype], B, Hq, Hkv, S, W, D, last,
+              _p(scores), _p(ws), ws.numel(), _stream(keys))
+    return scores
+
+
+def finch_score(q_pre: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, keys: torch.Tensor, normalize_scores: bool) -> torch.Tensor:
+    """FINCH scores (finch_press.py:56-83) from the PRE-RoPE window queries [B,Hq,W,D] (any W) and the window's cos/sin."""
+    return snapkv_score_rope(q_pre, cos, sin, keys, 1, _finch_normalize=bool(normalize_scores))
+
+
+def snapkv_score_from_attn(attn_win: torch.Tensor, num_kv_heads: int, k_len: int, kernel_size: int) -> torch.Tensor:
+    """Same from given attention weights: attn_win = attentions[..., -W:, :-W]  [B,Hq,W,S-W]."""
+    attn_win = _rows(attn_win)
+    B, Hq, W, Sm = attn_win.shape
+    S = int(k_len)
+    assert Sm == S - W, (attn_win.shape, S)
+    scores = torch.empty((B, num_kv_heads, S), dtype=torch.float32, device=attn_win.device)
+    with _on_device(attn_win.device):
+        ws = _scratch("kvp_snapkv_workspace_bytes", attn_win, B, Hq, num_kv_heads, S, W, 1)
+        _call("kvp_snapkv_score_from_attn", *_tensor(attn_win), _DTYPES[attn_win.dtype], B, Hq, num_kv_heads, S, W, int(kernel_size),
+              _p(scores), _p(ws), ws.numel(), _stream(attn_win))
+    return scores
+
+
+def ea_qstats(q: torch.Tensor, use_covariance: bool = True):
+    """mu [B,Hq,D], cov [B,Hq,D,D] (float32) of the queries q [B,Hq,Sq,D]."""
+    q = _rows(q)
+    B, Hq, Sq, D = q.shape
+    mu = torch.empty((B, Hq, D), dtype=torch.float32, device=q.device)
+    cov = torch.empty((B, Hq, D, D), dtype=torch.float32, device=q.device) if use_covariance else None
+    with _on_device(q.device):
+        ws = _scratch("kvp_ea_qstats_workspace_bytes", q, B, Hq, Sq, D)
+        _call("kvp_ea_qstats", *_tensor(q), _DTYPES[q.dtype], B, Hq, Sq, D, _p(mu), _p(cov), _p(ws), ws.numel(), _stream(q))
+    return mu, cov
+
+
+def ea_score(keys: torch.Tensor, values: torch.Tensor, mu: torch.Tensor, cov: Optional[torch.Tensor], n_sink: int,
+             use_vnorm: bool, epsilon: float) -> torch.Tensor:
+    """ExpectedAttention scores [B,Hkv,S] float32 (post-RoPE mu/cov float32 contiguous)."""
+    keys, values, B, Hkv, S, D = _kv(keys, values)
+    mu = mu.to(torch.float32).contiguous()
+    cov = cov.to(torch.float32).contiguous() if cov is not None else None
+    Hq = mu.shape[1]
+    assert mu.shape == (B, Hq, D) and (cov is None or cov.shape == (B, Hq, D, D))
+    scores = torch.empty((B, Hkv, S), dtype=torch.float32, device=keys.device)
+    with _on_device(keys.device):
+        ws = _scratch("kvp_ea_score_workspace_bytes", keys, B, Hq, Hkv, S, D)
+        _call("kvp_ea_score", *_tensor(keys), *_tensor(values), _DTYPES[keys.dtype], _p(mu), _p(cov), B, Hq, Hkv, S, D, int(n_sink),
+              int(bool(use_vnorm)), float(epsilon), _p(scores), _p(ws), ws.numel(), _stream(keys))
+    return scores
+
+
+def topk_select(scores: torch.Tensor, k: int, order: int = ORDER_POSITION) -> torch.Tensor:
+    """Indices (int32 [..., k]) of the k largest scores per row of float32 scores[..., S]; ties -> lowest position.
+    ``order | TOPK_SMALLEST`` selects the k smallest instead."""
+    if not scores.is_cuda:
+        raise KvpressHipError(f"kvpress_amd kernels need tensors on a HIP device, got {scores.device}")
+    s = scores.to(torch.float32)
+    if s.stride(-1) != 1:
+        s = s.contiguous()
+    S = s.shape[-1]
+    lead = s.shape[:-1]
+    s2 = s.reshape(-1, S)  # a view whenever possible
+    if s2.stride(-1) != 1 or (s2.shape[0] > 1 and s2.stride(0) < S):
+        s2 = s2.contiguous()
+    R = s2.shape[0]
+    idx = torch.empty((R, k), dtype=torch.int32, device=s.device)
+    if R and k:
+        with _on_device(s.device):
+            st = _stream(s)
+            if (int(order) & 0xFF) == ORDER_SCORE:
+                # descending-score order: the select's self-cleaning region first, then the sort's tiles and samples (never read before
+                # they are written)
+                ws = _clean_ws("order", (R, S, int(k)), lib().kvp_topk_order_workspace_bytes(R, S, k), s.device, st)
+            else:
+                # the layout (hence the clean region) depends on R and S only
+                ws = _clean_ws("topk", (R, S), lib().kvp_topk_workspace_bytes(R, S, k), s.device, st)
+            _call("kvp_topk_select", _p(s2), R, S, s2.stride(0) if R > 1 else S, int(k), int(order) | TOPK_WS_CLEAN, _p(idx),
+                  _p(ws), ws.numel(), st, clean_ws=ws)
+    return idx.reshape(*lead, k)
+
+
+def _gather(name: str, keys: torch.Tensor, values: torch.Tensor, idx: torch.Tensor, *extra):
+    keys, values, B, H, S, D = _kv(keys, values)
+    idx = idx.to(torch.int32).contiguous()
+    n = idx.shape[-1]
+    assert idx.shape == (B, H, n)
+    ko = torch.empty((B, H, n, D), dtype=keys.dtype, device=keys.device)
+    vo = torch.empty((B, H, n, D), dtype=values.dtype, device=values.device)
+    if B * H * n:
+        with _on_device(keys.device):
+            _call(name, *_tensor(keys), *_tensor(values), _DTYPES[keys.dtype], B, H, S, D, _p(idx), n, *extra, _p(ko), _p(vo), _stream(keys))
+    return ko, vo
+
+
+def gather_kv(keys: torch.Tensor, values: torch.Tensor, idx: torch.Tensor):
+    """K'[b,h,j] = K[b,h,idx[b,h,j]] (and V'), contiguous [B,H,n,D] in the input dtype."""
+    return _gather("kvp_gather_kv", keys, values, idx)
+
+
+def scores_fill_at_(scores: torch.Tensor, idx: torch.Tensor, value: float) -> torch.Tensor:
+    """In place: scores[..., idx[..., j]] = value (float32 scores [..., S] contiguous, int32 idx [..., n])."""
+    assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.is_cuda
+    S = scores.shape[-1]
+    idx = idx.to(torch.int32).contiguous()
+    n = idx.shape[-1]
+    R = scores.numel() // S if S else 0
+    assert idx.numel() == R * n
+    with _on_device(scores.device):
+        _call("kvp_scores_fill_at", _p(scores), R, S, S, _p(idx), n, float(value), _stream(scores))
+    return scores
+
+
+def topk_select_segmented(scores: torch.Tensor, seg_len: int, k: int, pos_base: int = 0) -> torch.Tensor:
+    """Per-chunk top-k: scores float32 [..., nseg * seg_len]; returns int32 [..., nseg * k] row positions (+ pos_base),
+    chunk after chunk (ascending)."""
+    if not scores.is_cuda:
+        raise KvpressHipError(f"kvpress_amd kernels need tensors on a HIP device, got {scores.device}")
+    s = scores.to(torch.float32).contiguous()
+    L = s.shape[-1]
+    assert L % seg_len == 0, (L, seg_len)
+    nseg = L // seg_len
+    lead = s.shape[:-1]
+    s2 = s.reshape(-1, L)
+    R = s2.shape[0]
+    idx = torch.empty((R, nseg * k), dtype=torch.int32, device=s.device)
+    if R and k:
+        with _on_device(s.device):
+            st = _stream(s)
+            # chunks of up to 32768 scores are selected by one workgroup each (topk_row_kernel): no workspace at all.  (Round 6: a fresh
+            # zero-filled 33 MB workspace per call was 11 us of ChunkPress's 128k step -- profiles/r06_rocprofv3_kernel_stats_chunk_snapkv128k.csv)
+            ws = None if seg_len <= 32768 else _clean_ws(
+                "seg", (R, nseg, int(seg_len)), lib().kvp_topk_segmented_workspace_bytes(R, nseg, seg_len, k), s.device, st)
+            _call("kvp_topk_select_segmented", _p(s2), R, nseg, int(seg_len), int(k), int(pos_base), TOPK_WS_CLEAN if ws is not None else 0,
+                  _p(idx), _p(ws), ws.numel() if ws is not None else 0, st, clean_ws=ws)
+    return idx.reshape(*lead, nseg * k)
+
+
+def rerotate_keys_(keys_kept: torch.Tensor, idx: torch.Tensor, inv_freq: torch.Tensor) -> torch.Tensor:
+    """In place: re-rotate gathered keys [B,H,n,D] (kept at ascending positions idx [B,H,n]) to positions 0..n-1."""
+    _dev(keys_kept)
+    assert keys_kept.is_contiguous()
+    B, H, n, D = keys_kept.shape
+    idx = idx.to(torch.int32).contiguous()
+    assert idx.shape == (B, H, n)
+    inv = inv_freq.to(device=keys_kept.device, dtype=torch.float32).contiguous()
+    assert inv.numel() == D // 2
+    with _on_device(keys_kept.device):
+        _call("kvp_rerotate_keys", _p(keys_kept), _DTYPES[keys_kept.dtype], B, H, n, D, _p(idx), _p(inv), _stream(keys_kept))
+    return keys_kept
+
+
+def gather_kv_rerotate(keys: torch.Tensor, values: torch.Tensor, idx: torch.Tensor, inv_freq: torch.Tensor):
+    """gather_kv + rerotate_keys_ in one pass: K'[b,h,j] = K[b,h,idx[b,h,j]] re-rotated from position idx[b,h,j] to position j, V' the
+    plain gather (same bits as the two calls)."""
+    inv = inv_freq.to(device=keys.device, dtype=torch.float32).contiguous()
+    assert inv.numel() == keys.shape[3] // 2
+    return _gather("kvp_gather_kv_rerotate", keys, values, idx, _p(inv))
+
+
+def knorm_compress(keys: torch.Tensor, values: torch.Tensor, n_kept: int, order: int = ORDER_POSITION):
+    """KnormPress.compress in one library call: (K', V') contiguous [B,H,n_kept,D]; order = ORDER_SCORE stores the rows in descending
+    score order (the reference's layout)."""
+    keys, values, B, H, S, D = _kv(keys, values)
+    n = int(n_kept)
+    return _fused_compress("kvp_knorm_compress", "knorm", (B, H, S, n), keys, H, n, order, bool(n and B and H),
+                           *_tensor(keys), *_tensor(values), _DTYPES[keys.dtype], B, H, S, D)
+
+
+def snapkv_compress_rope(q_pre: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, keys: torch.Tensor, values: torch.Tensor,
+                         kernel_size: int, n_kept: int, order: int = ORDER_POSITION):
+    """SnapKVPress.compress (attentions=None) in one library call from the pre-RoPE window queries; order = ORDER_SCORE stores the rows
+    in descending score order (window tokens first: the reference's layout)."""
+    keys, values, _, _, _, _ = _kv(keys, values)
+    q_pre, B, Hq, Hkv, S, W, D = _queries(q_pre, keys)
+    cos, sin = _rotary(cos, sin, keys.dtype, (B, W, D))
+    n = int(n_kept)
+    return _fused_compress("kvp_snapkv_compress_rope", "snapkv", (B, Hq, Hkv, S, W, D, n), keys, Hkv, n, order, bool(n),
+                           *_tensor(q_pre), *_tables(cos, sin), *_tensor(keys), *_tensor(values), _DTYPES[keys.dtype],
+                           B, Hq, Hkv, S, W, D, int(kernel_size))
 
 
 def keydiff_score(keys: torch.Tensor) -> torch.Tensor:
     """KeyDiff scores [B,H,S] float32: -cos(k, mean of the normalised keys of the head)."""
-    keys = _rows_last_contig(_dev(keys))
+    keys = _rows(keys)
     B, H, S, D = keys.shape
+    ptr, *strides = _tensor(keys)
     scores = torch.empty((B, H, S), dtype=torch.float32, device=keys.device)
     with _on_device(keys.device):
-        nws = lib().kvp_keydiff_workspace_bytes(B, H, S, D)
-        ws = _ws(nws, keys)
-        _check(lib().kvp_keydiff_score(_p(keys), _DTYPES[keys.dtype], B, H, S, D, _st(keys, 0), _st(keys, 1), _st(keys, 2),
-                                       _p(scores), _p(ws), ws.numel(), _stream(keys)), "kvp_keydiff_score")
+        ws = _scratch("kvp_keydiff_workspace_bytes", keys, B, H, S, D)
+        _call("kvp_keydiff_score", ptr, _DTYPES[keys.dtype], B, H, S, D, *strides, _p(scores), _p(ws), ws.numel(), _stream(keys))
+    return scores
+
+
+def cur_score(keys: torch.Tensor, values: torch.Tensor, leverage_type: str, local_window_size: int, num_sinks: int) -> torch.Tensor:
+    """CUR leverage scores [B,H,S] float32 (local_window_size 0 = no local approximation)."""
+    keys, values, B, H, S, D = _kv(keys, values, same=False)
+    assert keys.dtype == values.dtype and keys.shape[:3] == values.shape[:3] and keys.shape[3] == values.shape[3]
+    if leverage_type not in CUR_LEVERAGE:
+        raise ValueError("Unknown leverage type: choose from 'kv_avg', 'key', 'value' or 'kv_product'")
+    scores = torch.empty((B, H, S), dtype=torch.float32, device=keys.device)
+    with _on_device(keys.device):
+        ws = _scratch("kvp_cur_workspace_bytes", keys, B, H, S)
+        _call("kvp_cur_score", *_tensor(keys), *_tensor(values), _DTYPES[keys.dtype], B, H, S, D, CUR_LEVERAGE[leverage_type],
+              int(local_window_size), int(num_sinks), _p(scores), _p(ws), ws.numel(), _stream(keys))
     return scores
 
 
@@ -347,76 +602,153 @@ def scores_head_mean_(scores: torch.Tensor) -> torch.Tensor:
     assert scores.dtype == torch.float32 and scores.dim() == 3 and scores.stride(2) == 1
     _dev(scores)
     B, H, S = scores.shape
+    ptr, *strides = _tensor(scores, 2)
     with _on_device(scores.device):
-        _check(lib().kvp_scores_head_mean(_p(scores), B, H, S, _st(scores, 0), _st(scores, 1), _stream(scores)),
-               "kvp_scores_head_mean")
+        _call("kvp_scores_head_mean", ptr, B, H, S, *strides, _stream(scores))
     return scores
 
 
-def snapkv_score(q_win: torch.Tensor, keys: torch.Tensor, kernel_size: int) -> torch.Tensor:
-    """SnapKV scores [B,Hkv,S] float32 from RoPE'd window queries [B,Hq,W,D] and keys [B,Hkv,S,D]."""
-    keys = _rows_last_contig(_dev(keys))
-    q_win = _rows_last_contig(_dev(q_win))
-    if q_win.dtype != keys.dtype:
-        q_win = q_win.to(keys.dtype)
-    B, Hq, W, D = q_win.shape
-    Bk, Hkv, S, Dk = keys.shape
-    assert B == Bk and D == Dk and Hq % Hkv == 0, (q_win.shape, keys.shape)
+def _hidden(hidden_win, wq, cos, sin, dt):
+    """The window's hidden states, the q_proj weight and the rotary tables as the library's own projection takes them."""
+    hidden_win = _dev(hidden_win)
+    assert hidden_win.dtype == dt and wq.dtype == dt and hidden_win.stride(-1) == 1 and wq.is_contiguous()
+    return (hidden_win, *_rotary(cos, sin, dt))
+
+
+def _hidden_keys(hidden_win, wq, cos, sin, keys):
+    """_hidden for prepared keys [B,Hkv,S,D]: the three tensors, then B, Hq, Hkv, S, W, D and the hidden size K."""
+    hidden_win, cos, sin = _hidden(hidden_win, wq, cos, sin, keys.dtype)
+    B, W, K = hidden_win.shape
+    Bk, Hkv, S, D = keys.shape
+    Hq = wq.shape[0] // D
+    assert B == Bk and Hq % Hkv == 0
+    return hidden_win, cos, sin, B, Hq, Hkv, S, W, D, K
+
+
+def snapkv_qproj_rope(hidden_win: torch.Tensor, wq: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, head_dim: int = 128) -> torch.Tensor:
+    """RoPE'd window queries [B, Hq, W, D] from hidden_states[:, -W:] and q_proj.weight (bf16 / f16, W = 64, D = 128)."""
+    dt = hidden_win.dtype
+    hidden_win, cos, sin = _hidden(hidden_win, wq, cos, sin, dt)
+    B, W, K = hidden_win.shape
+    Hq = wq.shape[0] // head_dim
+    out = torch.empty((B, Hq, W, head_dim), dtype=dt, device=hidden_win.device)
+    with _on_device(hidden_win.device):
+        _call("kvp_snapkv_qproj_rope", *_tensor(hidden_win, 2), _p(wq), *_tables(cos, sin), _DTYPES[dt], B, Hq, W, head_dim, K,
+              _p(out), _stream(hidden_win))
+    return out
+
+
+def snapkv_score_hidden(hidden_win: torch.Tensor, wq: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, keys: torch.Tensor,
+                        kernel_size: int) -> torch.Tensor:
+    """SnapKV scores [B,Hkv,S] float32 from the window's hidden states and the q_proj weight (projection + RoPE in the library)."""
+    keys = _rows(keys)
+    hidden_win, cos, sin, B, Hq, Hkv, S, W, D, K = _hidden_keys(hidden_win, wq, cos, sin, keys)
     scores = torch.empty((B, Hkv, S), dtype=torch.float32, device=keys.device)
     with _on_device(keys.device):
-        nws = lib().kvp_snapkv_workspace_bytes(B, Hq, Hkv, S, W, D)
-        ws = _ws(nws, keys)
-        _check(lib().kvp_snapkv_score(_p(q_win), _st(q_win, 0), _st(q_win, 1), _st(q_win, 2),
-                                      _p(keys), _st(keys, 0), _st(keys, 1), _st(keys, 2), _DTYPES[keys.dtype],
-                                      B, Hq, Hkv, S, W, D, int(kernel_size), _p(scores), _p(ws), ws.numel(), _stream(keys)),
-               "kvp_snapkv_score")
+        ws = _scratch("kvp_snapkv_workspace_bytes", keys, B, Hq, Hkv, S, W, D)
+        _call("kvp_snapkv_score_hidden", *_tensor(hidden_win, 2), _p(wq), K, *_tables(cos, sin), *_tensor(keys), _DTYPES[keys.dtype],
+              B, Hq, Hkv, S, W, D, int(kernel_size), _p(scores), _p(ws), ws.numel(), _stream(keys))
     return scores
 
 
-def _window_tables(cos: torch.Tensor, sin: torch.Tensor, B: int, W: int, D: int):
-    """The window's rotary tables as the library takes them: [1 or B, W, D] with equal strides.  A table with ONE row is
-    broadcast over the window (stride 0), which is what the reference's ``cos[:, -W:].unsqueeze(1)`` does when a decoding
-    step hands over the current position only (DecodingPress with a window scorer)."""
-    assert cos.shape == sin.shape and cos.shape[-1] == D and cos.shape[0] in (1, B) and cos.shape[-2] in (1, W), (cos.shape, (B, W, D))
-    if sin.stride() != cos.stride():
-        sin, cos = sin.contiguous(), cos.contiguous()
-    if cos.shape[-2] == 1 and W > 1:
-        cos, sin = cos.expand(-1, W, -1), sin.expand(-1, W, -1)
-    return cos, sin
+def snapkv_compress_hidden(hidden_win: torch.Tensor, wq: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, keys: torch.Tensor,
+                           values: torch.Tensor, kernel_size: int, n_kept: int, order: int = ORDER_POSITION):
+    """SnapKVPress.compress (attentions=None) in one library call from the window's hidden states (order: see snapkv_compress_rope)."""
+    keys, values, _, _, _, _ = _kv(keys, values)
+    hidden_win, cos, sin, B, Hq, Hkv, S, W, D, K = _hidden_keys(hidden_win, wq, cos, sin, keys)
+    n = int(n_kept)
+    return _fused_compress("kvp_snapkv_compress_hidden", "snapkv", (B, Hq, Hkv, S, W, D, n), keys, Hkv, n, order, bool(n),
+                           *_tensor(hidden_win, 2), _p(wq), K, *_tables(cos, sin), *_tensor(keys), *_tensor(values), _DTYPES[keys.dtype],
+                           B, Hq, Hkv, S, W, D, int(kernel_size))
 
 
-def finch_score(q_pre: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, keys: torch.Tensor, normalize_scores: bool) -> torch.Tensor:
-    """FINCH scores (finch_press.py:56-83) from the PRE-RoPE window queries [B,Hq,W,D] (any W) and the window's cos/sin."""
-    return snapkv_score_rope(q_pre, cos, sin, keys, 1, _finch_normalize=bool(normalize_scores))
-
-
-def snapkv_score_rope(q_pre: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, keys: torch.Tensor,
-                      kernel_size: int, _finch_normalize=None) -> torch.Tensor:
-    """SnapKV scores from the PRE-RoPE window queries [B,Hq,W,D] and the window's cos/sin [1 or B, W, D]:
-    the RoPE (q*cos + rotate_half(q)*sin, rounded like torch does in the model dtype) runs in the library."""
-    keys = _rows_last_contig(_dev(keys))
-    q_pre = _rows_last_contig(_dev(q_pre))
+# the Compactor family (non_causal_attention_press.py, leverage_press.py, compactor_press.py)
+def ncattn_score(q_pre: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, keys: torch.Tensor, values: torch.Tensor, chunk_size: int,
+                 return_raw: bool = False):
+    """NonCausalAttnPress scores (non_causal_attention_press.py:95-122): z-scores [B,Hkv,S] float32 from the PRE-RoPE queries
+    [B,Hq,S,D], the rotary tables of the same S positions [1 or B, S, D], keys and values [B,Hkv,S,D]; with ``return_raw`` also the
+    scores before the z-score."""
+    keys, values, _, Hkv, _, _ = _kv(keys, values, same=False)
+    q_pre = _rows(q_pre)
     dt = keys.dtype
     if q_pre.dtype != dt:
         q_pre = q_pre.to(dt)
-    cos = _rows_last_contig(_dev(cos.to(dt)))
-    sin = _rows_last_contig(_dev(sin.to(dt)))
-    B, Hq, W, D = q_pre.shape
-    Bk, Hkv, S, Dk = keys.shape
-    assert B == Bk and D == Dk and Hq % Hkv == 0, (q_pre.shape, keys.shape)
-    cos, sin = _window_tables(cos, sin, B, W, D)
-    scores = torch.empty((B, Hkv, S), dtype=torch.float32, device=keys.device)
+    if values.dtype != dt:
+        values = values.to(dt)
+    B, Hq, S, D = q_pre.shape
+    assert keys.shape == (B, Hkv, S, D) and tuple(values.shape[:3]) == (B, Hkv, S) and values.shape[3] == D, (q_pre.shape, keys.shape, values.shape)
+    if Hq % Hkv != 0:
+        raise KvpressHipError(f"kvp_ncattn_score: Hq % Hkv != 0 ({Hq}, {Hkv})")
+    cos, sin = _rotary(cos, sin, dt)
+    assert cos.shape == sin.shape and cos.shape[-1] == D and cos.shape[-2] == S and cos.shape[0] in (1, B), (cos.shape, q_pre.shape)
+    raw = torch.empty((B, Hkv, S), dtype=torch.float32, device=keys.device) if return_raw else None
+    z = torch.empty((B, Hkv, S), dtype=torch.float32, device=keys.device)
     with _on_device(keys.device):
-        nws = lib().kvp_snapkv_workspace_bytes(B, Hq, Hkv, S, W, D)
-        ws = _ws(nws, keys)
-        fn, last, what = ((lib().kvp_snapkv_score_rope, int(kernel_size), "kvp_snapkv_score_rope") if _finch_normalize is None
-                          else (lib().kvp_finch_score, int(_finch_normalize), "kvp_finch_score"))
-        _check(fn(_p(q_pre), _st(q_pre, 0), _st(q_pre, 1), _st(q_pre, 2), _p(cos), _p(sin), _st(cos, 0), _st(cos, 1), _p(keys),
-                  _st(keys, 0), _st(keys, 1), _st(keys, 2), _DTYPES[dt], B, Hq, Hkv, S, W, D, last, _p(scores), _p(ws), ws.numel(),
-                  _stream(keys)), what)
-    return scores
+        ws = _scratch("kvp_ncattn_workspace_bytes", keys, B, Hkv, S)
+        _call("kvp_ncattn_score", *_tensor(q_pre), *_tables(cos, sin), *_tensor(keys), *_tensor(values), _DTYPES[dt], B, Hq, Hkv, S, D,
+              int(chunk_size), _p(raw), _p(z), _p(ws), ws.numel(), _stream(keys))
+    return (z, raw) if return_raw else z
 
 
+def leverage_score(keys_pre: torch.Tensor, phi: torch.Tensor, return_raw: bool = False):
+    """LeverageScorePress scores (leverage_press.py:59-110): z-scores [B,H,S] float32 from the PRE-RoPE keys [B,H,S,D] and the
+    Gaussian sketch phi [B,H,D,k] (drawn by the caller, leverage_press.py:68-75).  Synchronises the stream to check the Cholesky
+    factorisation, as the reference does; raises KvpressHipError("... Cholesky failed after 5 tries ...") like its RuntimeError."""
+    k, phi = _rows(keys_pre), _rows(phi)
+    if phi.dtype != k.dtype:
+        phi = phi.to(k.dtype)
+    B, H, S, D = k.shape
+    assert tuple(phi.shape[:3]) == (B, H, D), (phi.shape, k.shape)
+    ks = phi.shape[3]
+    raw = torch.empty((B, H, S), dtype=torch.float32, device=k.device) if return_raw else None
+    z = torch.empty((B, H, S), dtype=torch.float32, device=k.device)
+    with _on_device(k.device):
+        ws = _scratch("kvp_leverage_workspace_bytes", k, B, H, S, D, ks)
+        _call("kvp_leverage_score", *_tensor(k), *_tensor(phi), _DTYPES[k.dtype], B, H, S, D, ks, _p(raw), _p(z), _p(ws), ws.numel(), _stream(k))
+        _call("kvp_leverage_status", _p(ws), B, H, S, D, ks, _stream(k), what="kvp_leverage_score")
+    return (z, raw) if return_raw else z
+
+
+def compactor_combine(z_lev: torch.Tensor, z_attn: torch.Tensor, sink_start: int, sink_end: int, blending: float) -> torch.Tensor:
+    """blending * z_lev + z_attn, padded with sink_start / sink_end positions holding the global max (compactor_press.py:119-122)."""
+    z_lev = _dev(z_lev).contiguous()
+    z_attn = _dev(z_attn).contiguous()
+    assert z_lev.shape == z_attn.shape and z_lev.dtype == torch.float32 and z_attn.dtype == torch.float32, (z_lev.shape, z_attn.shape)
+    B, H, Si = z_lev.shape
+    out = torch.empty((B, H, Si + sink_start + sink_end), dtype=torch.float32, device=z_lev.device)
+    with _on_device(z_lev.device):
+        ws = _scratch("kvp_compactor_combine_workspace_bytes", z_lev)
+        _call("kvp_compactor_combine", _p(z_lev), _p(z_attn), B, H, Si, int(sink_start), int(sink_end), float(blending), _p(out), _p(ws),
+              ws.numel(), _stream(z_lev))
+    return out
+
+
+# MergingPress (merging_press.py:99-177)
+def merge_values_(keys: torch.Tensor, values: torch.Tensor, kept_idx: torch.Tensor, k_out: torch.Tensor, v_out: torch.Tensor,
+                  threshold: float, fraction: float, target: Optional[torch.Tensor] = None, max_sim: Optional[torch.Tensor] = None):
+    """MergingPress.merge after the select and the gather: folds every evicted token's value (keys / values [B,H,S,D], evicted = not in
+    the int32 kept_idx [B,H,n_kept]) into its most cosine-similar kept row, IN PLACE in v_out (the contiguous gathered V'; k_out is the
+    gathered K').  ``target`` (int32) / ``max_sim`` (float32) [B,H,S-n_kept], if given, receive the argmax and its cosine.  Returns v_out."""
+    keys, values, B, H, S, D = _kv(keys, values, same=False)
+    dt = keys.dtype
+    assert values.dtype == dt and tuple(values.shape) == (B, H, S, D), (keys.shape, values.shape)
+    n = kept_idx.shape[-1]
+    assert tuple(kept_idx.shape) == (B, H, n) and kept_idx.dtype == torch.int32 and kept_idx.is_contiguous(), (kept_idx.shape, kept_idx.dtype)
+    for t in (k_out, v_out):
+        assert t.dtype == dt and tuple(t.shape) == (B, H, n, D) and t.is_contiguous() and t.device == keys.device, (t.shape, t.dtype)
+    for t, tdt in ((target, torch.int32), (max_sim, torch.float32)):
+        if t is not None:
+            assert t.dtype == tdt and tuple(t.shape) == (B, H, S - n) and t.is_contiguous(), (t.shape, t.dtype)
+    if n == 0 or n == S:
+        return v_out
+    with _on_device(keys.device):
+        ws = _scratch("kvp_merge_workspace_bytes", keys, B, H, S, n, D)
+        _call("kvp_merge_values", *_tensor(keys), *_tensor(values), _p(kept_idx), _p(k_out), _p(v_out), _DTYPES[dt], B, H, S, n, D,
+              float(threshold), float(fraction), _p(ws), ws.numel(), _p(target), _p(max_sim), _stream(keys))
+    return v_out
+
+
+# ---- the q_proj eligibility logic ---------------------------------------------------------------------------------------------------
 # The window q_proj + RoPE of the SnapKV-type presses run in the library (qproj.hip) for a plain bias-free bf16 / f16 nn.Linear
 # (qproj_rope_eligible): inside bench.py's loop the step is 3-4 us shorter than with the model's own GEMM + the RoPE launch
 # (round 4, two boxes, alternating runs: profiles/r04_qproj_lab.txt; rounds 1-2 had measured parity in isolation and kept it off).
@@ -480,381 +812,60 @@ def _qproj_rope_eligible_slow(module, hidden_states: torch.Tensor, window: int) 
             and hidden_states.stride(-1) == 1 and w.shape[0] == module.config.num_attention_heads * 128)
 
 
-def _hidden_args(hidden_win, wq, cos, sin, dt):
-    hidden_win = _dev(hidden_win)
-    assert hidden_win.dtype == dt and wq.dtype == dt and hidden_win.stride(-1) == 1 and wq.is_contiguous()
-    cos = _rows_last_contig(_dev(cos.to(dt)))
-    sin = _rows_last_contig(_dev(sin.to(dt)))
-    if sin.stride() != cos.stride():
-        sin, cos = sin.contiguous(), cos.contiguous()
-    return hidden_win, cos, sin
-
-
-def snapkv_qproj_rope(hidden_win: torch.Tensor, wq: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, head_dim: int = 128) -> torch.Tensor:
-    """RoPE'd window queries [B, Hq, W, D] from hidden_states[:, -W:] and q_proj.weight (bf16 / f16, W = 64, D = 128)."""
-    dt = hidden_win.dtype
-    hidden_win, cos, sin = _hidden_args(hidden_win, wq, cos, sin, dt)
-    B, W, K = hidden_win.shape
-    Hq = wq.shape[0] // head_dim
-    out = torch.empty((B, Hq, W, head_dim), dtype=dt, device=hidden_win.device)
-    with _on_device(hidden_win.device):
-        _check(lib().kvp_snapkv_qproj_rope(_p(hidden_win), _st(hidden_win, 0), _st(hidden_win, 1), _p(wq), _p(cos), _p(sin), _st(cos, 0),
-                                           _st(cos, 1), _DTYPES[dt], B, Hq, W, head_dim, K, _p(out), _stream(hidden_win)),
-               "kvp_snapkv_qproj_rope")
+# ---- contrib wrappers: include/kvpress_hip_extra.h, libkvpress_hip_contrib.so ----------------------------------------------------------
+def observed_attention_score(attentions: torch.Tensor, num_kv_heads: int) -> torch.Tensor:
+    """Average attention weight every key receives (observed_attention_press.py:42-48): attentions [B,Hq,Sq,S] -> [B,Hkv,S] float32."""
+    a = _rows(attentions)
+    B, Hq, Sq, S = a.shape
+    assert Hq % num_kv_heads == 0, (a.shape, num_kv_heads)
+    out = torch.empty((B, num_kv_heads, S), dtype=torch.float32, device=a.device)
+    with _on_device(a.device):
+        _call("kvp_observed_attention_score", *_tensor(a), _DTYPES[a.dtype], B, Hq, num_kv_heads, Sq, S, _p(out), _stream(a),
+              contrib=True)
     return out
 
 
-def snapkv_score_hidden(hidden_win: torch.Tensor, wq: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, keys: torch.Tensor,
-                        kernel_size: int) -> torch.Tensor:
-    """SnapKV scores [B,Hkv,S] float32 from the window's hidden states and the q_proj weight (projection + RoPE in the library)."""
-    keys = _rows_last_contig(_dev(keys))
-    dt = keys.dtype
-    hidden_win, cos, sin = _hidden_args(hidden_win, wq, cos, sin, dt)
-    B, W, K = hidden_win.shape
-    Bk, Hkv, S, D = keys.shape
-    Hq = wq.shape[0] // D
-    assert B == Bk and Hq % Hkv == 0
-    scores = torch.empty((B, Hkv, S), dtype=torch.float32, device=keys.device)
+def lagkv_score(keys: torch.Tensor, values: torch.Tensor, n_sink: int, lag_size: int, cross_scoring: bool) -> torch.Tensor:
+    """LagKV scores [B,H,S] float32 (lagkv_press.py:56-97) for S >= n_sink + 2 * lag_size."""
+    keys, values, B, H, S, D = _kv(keys, values)
+    out = torch.empty((B, H, S), dtype=torch.float32, device=keys.device)
     with _on_device(keys.device):
-        ws = _ws(lib().kvp_snapkv_workspace_bytes(B, Hq, Hkv, S, W, D), keys)
-        _check(lib().kvp_snapkv_score_hidden(_p(hidden_win), _st(hidden_win, 0), _st(hidden_win, 1), _p(wq), K, _p(cos), _p(sin),
-                                             _st(cos, 0), _st(cos, 1), _p(keys), _st(keys, 0), _st(keys, 1), _st(keys, 2), _DTYPES[dt],
-                                             B, Hq, Hkv, S, W, D, int(kernel_size), _p(scores), _p(ws), ws.numel(), _stream(keys)),
-               "kvp_snapkv_score_hidden")
-    return scores
+        _call("kvp_lagkv_score", *_tensor(keys), *_tensor(values), _DTYPES[keys.dtype], B, H, S, D, int(n_sink), int(lag_size),
+              int(bool(cross_scoring)), _p(out), _stream(keys), contrib=True)
+    return out
 
 
-def snapkv_compress_hidden(hidden_win: torch.Tensor, wq: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, keys: torch.Tensor,
-                           values: torch.Tensor, kernel_size: int, n_kept: int, order: int = ORDER_POSITION):
-    """SnapKVPress.compress (attentions=None) in one library call from the window's hidden states (order: see snapkv_compress_rope)."""
-    keys = _rows_last_contig(_dev(keys))
-    values = _rows_last_contig(_dev(values))
-    dt = keys.dtype
-    assert values.dtype == dt and keys.shape == values.shape
-    hidden_win, cos, sin = _hidden_args(hidden_win, wq, cos, sin, dt)
-    B, W, K = hidden_win.shape
-    Bk, Hkv, S, D = keys.shape
-    Hq = wq.shape[0] // D
-    assert B == Bk and Hq % Hkv == 0
-    n = int(n_kept)
-    ko = torch.empty((B, Hkv, n, D), dtype=dt, device=keys.device)
-    vo = torch.empty_like(ko)
-    if n:
-        with _on_device(keys.device):
-            st = _stream(keys)
-            ws = _clean_ws("snapkv", (B, Hq, Hkv, S, W, D, n), _ws_bytes("kvp_snapkv_compress_workspace_bytes", B, Hq, Hkv, S, W, D, n), keys, st)
-            rc = lib().kvp_snapkv_compress_hidden(_p(hidden_win), _st(hidden_win, 0), _st(hidden_win, 1), _p(wq), K, _p(cos), _p(sin),
-                                                  _st(cos, 0), _st(cos, 1), _p(keys), _st(keys, 0), _st(keys, 1), _st(keys, 2),
-                                                  _p(values), _st(values, 0), _st(values, 1), _st(values, 2), _DTYPES[dt], B, Hq, Hkv, S,
-                                                  W, D, int(kernel_size), n, _p(ko), _p(vo), _p(ws), ws.numel(), TOPK_WS_CLEAN | (int(order) & ORDER_SCORE), st)
-            if rc != 0:
-                _drop_ws(ws)
-            _check(rc, "kvp_snapkv_compress_hidden")
-    return ko, vo
-
-
-def snapkv_score_from_attn(attn_win: torch.Tensor, num_kv_heads: int, k_len: int, kernel_size: int) -> torch.Tensor:
-    """Same from given attention weights: attn_win = attentions[..., -W:, :-W]  [B,Hq,W,S-W]."""
-    attn_win = _rows_last_contig(_dev(attn_win))
-    B, Hq, W, Sm = attn_win.shape
-    S = int(k_len)
-    assert Sm == S - W, (attn_win.shape, S)
-    scores = torch.empty((B, num_kv_heads, S), dtype=torch.float32, device=attn_win.device)
-    with _on_device(attn_win.device):
-        nws = lib().kvp_snapkv_workspace_bytes(B, Hq, num_kv_heads, S, W, 1)
-        ws = _ws(nws, attn_win)
-        _check(lib().kvp_snapkv_score_from_attn(_p(attn_win), _st(attn_win, 0), _st(attn_win, 1), _st(attn_win, 2),
-                                                _DTYPES[attn_win.dtype], B, Hq, num_kv_heads, S, W, int(kernel_size),
-                                                _p(scores), _p(ws), ws.numel(), _stream(attn_win)),
-               "kvp_snapkv_score_from_attn")
-    return scores
-
-
-def ea_qstats(q: torch.Tensor, use_covariance: bool = True):
-    """mu [B,Hq,D], cov [B,Hq,D,D] (float32) of the queries q [B,Hq,Sq,D]."""
-    q = _rows_last_contig(_dev(q))
-    B, Hq, Sq, D = q.shape
-    mu = torch.empty((B, Hq, D), dtype=torch.float32, device=q.device)
-    cov = torch.empty((B, Hq, D, D), dtype=torch.float32, device=q.device) if use_covariance else None
-    with _on_device(q.device):
-        nws = lib().kvp_ea_qstats_workspace_bytes(B, Hq, Sq, D)
-        ws = _ws(nws, q)
-        _check(lib().kvp_ea_qstats(_p(q), _st(q, 0), _st(q, 1), _st(q, 2), _DTYPES[q.dtype], B, Hq, Sq, D,
-                                   _p(mu), _p(cov), _p(ws), ws.numel(), _stream(q)), "kvp_ea_qstats")
-    return mu, cov
-
-
-def ea_score(keys: torch.Tensor, values: torch.Tensor, mu: torch.Tensor, cov: Optional[torch.Tensor], n_sink: int,
-             use_vnorm: bool, epsilon: float) -> torch.Tensor:
-    """ExpectedAttention scores [B,Hkv,S] float32 (post-RoPE mu/cov float32 contiguous)."""
-    keys = _rows_last_contig(_dev(keys))
-    values = _rows_last_contig(_dev(values))
-    assert keys.dtype == values.dtype and keys.shape == values.shape
-    B, Hkv, S, D = keys.shape
-    mu = mu.to(torch.float32).contiguous()
-    cov = cov.to(torch.float32).contiguous() if cov is not None else None
-    Hq = mu.shape[1]
-    assert mu.shape == (B, Hq, D) and (cov is None or cov.shape == (B, Hq, D, D))
-    scores = torch.empty((B, Hkv, S), dtype=torch.float32, device=keys.device)
+def think_channel_scores(q_win: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
+    """ThinK's per-channel scores [B,Hkv,D] float32 (think_press.py:72-76) from the RoPE'd window queries [B,Hq,W,D] and keys."""
+    keys = _rows(keys)
+    q_win, B, Hq, Hkv, S, W, D = _queries(q_win, keys)
+    out = torch.empty((B, Hkv, D), dtype=torch.float32, device=keys.device)
     with _on_device(keys.device):
-        nws = lib().kvp_ea_score_workspace_bytes(B, Hq, Hkv, S, D)
-        ws = _ws(nws, keys)
-        _check(lib().kvp_ea_score(_p(keys), _st(keys, 0), _st(keys, 1), _st(keys, 2),
-                                  _p(values), _st(values, 0), _st(values, 1), _st(values, 2), _DTYPES[keys.dtype],
-                                  _p(mu), _p(cov), B, Hq, Hkv, S, D, int(n_sink), int(bool(use_vnorm)), float(epsilon),
-                                  _p(scores), _p(ws), ws.numel(), _stream(keys)), "kvp_ea_score")
-    return scores
+        ws = _scratch("kvp_think_workspace_bytes", keys, B, Hkv, S, D, contrib=True)
+        _call("kvp_think_channel_scores", *_tensor(q_win), *_tensor(keys), _DTYPES[keys.dtype], B, Hq, Hkv, S, W, D, _p(out), _p(ws), ws.numel(),
+              _stream(keys), contrib=True)
+    return out
 
 
-TOPK_SMALLEST = 0x200
-
-
-def scores_fill_at_(scores: torch.Tensor, idx: torch.Tensor, value: float) -> torch.Tensor:
-    """In place: scores[..., idx[..., j]] = value (float32 scores [..., S] contiguous, int32 idx [..., n])."""
-    assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.is_cuda
-    S = scores.shape[-1]
+def zero_channels_(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """x[b,h,:,idx[b,h,j]] = 0 in place (think_press.py:81-82); x [B,H,S,D] with a contiguous last dim, idx [B,H,n] int32."""
+    assert x.is_cuda and x.stride(-1) == 1, "zero_channels_ works in place on a device tensor with contiguous rows"
+    B, H, S, D = x.shape
+    assert idx.is_cuda and idx.device == x.device and tuple(idx.shape[:2]) == (B, H), (idx.shape, x.shape)
     idx = idx.to(torch.int32).contiguous()
-    n = idx.shape[-1]
-    R = scores.numel() // S if S else 0
-    assert idx.numel() == R * n
-    with _on_device(scores.device):
-        _check(lib().kvp_scores_fill_at(_p(scores), R, S, S, _p(idx), n, float(value), _stream(scores)), "kvp_scores_fill_at")
-    return scores
+    with _on_device(x.device):
+        _call("kvp_zero_channels", *_tensor(x), _DTYPES[x.dtype], B, H, S, D, _p(idx), idx.shape[2], _stream(x), contrib=True)
+    return x
 
 
-def topk_select(scores: torch.Tensor, k: int, order: int = ORDER_POSITION) -> torch.Tensor:
-    """Indices (int32 [..., k]) of the k largest scores per row of float32 scores[..., S]; ties -> lowest position.
-    ``order | TOPK_SMALLEST`` selects the k smallest instead."""
-    if not scores.is_cuda:
-        raise KvpressHipError(f"kvpress_amd kernels need tensors on a HIP device, got {scores.device}")
-    s = scores.to(torch.float32)
-    if s.stride(-1) != 1:
-        s = s.contiguous()
-    S = s.shape[-1]
-    lead = s.shape[:-1]
-    s2 = s.reshape(-1, S)  # a view whenever possible
-    if s2.stride(-1) != 1 or (s2.shape[0] > 1 and s2.stride(0) < S):
-        s2 = s2.contiguous()
-    R = s2.shape[0]
-    idx = torch.empty((R, k), dtype=torch.int32, device=s.device)
-    if R and k:
-        with _on_device(s.device):
-            stream = torch.cuda.current_stream(s.device)
-            if (int(order) & 0xFF) == ORDER_SCORE:
-                # descending-score order: the select's self-cleaning region first, then the sort's tiles and samples (never read before
-                # they are written): one cached workspace per (device, stream, shape), zero-filled once like the plain select's
-                nws = lib().kvp_topk_order_workspace_bytes(R, S, k)
-                ws = _cached_ws(("order", s.device.index, stream.cuda_stream, R, S, int(k)), nws, s.device)
-            else:
-                nws = lib().kvp_topk_workspace_bytes(R, S, k)
-                # self-cleaning workspace: zeroed once per (device, stream, size), reused with KVP_TOPK_WS_CLEAN
-                key = (s.device.index, stream.cuda_stream, R, S)  # the layout (hence the clean region) depends on R and S
-                ws = _cached_ws(key, nws, s.device)
-            try:
-                _check(lib().kvp_topk_select(_p(s2), R, S, s2.stride(0) if R > 1 else S, int(k), int(order) | TOPK_WS_CLEAN, _p(idx),
-                                             _p(ws), ws.numel(), _stream(s)), "kvp_topk_select")
-            except KvpressHipError:
-                _drop_ws(ws)  # a failed call may leave dirty histograms behind: never reuse this workspace as "clean"
-                raise
-    return idx.reshape(*lead, k)
-
-
-def topk_select_segmented(scores: torch.Tensor, seg_len: int, k: int, pos_base: int = 0) -> torch.Tensor:
-    """Per-chunk top-k: scores float32 [..., nseg * seg_len]; returns int32 [..., nseg * k] row positions (+ pos_base),
-    chunk after chunk (ascending)."""
-    if not scores.is_cuda:
-        raise KvpressHipError(f"kvpress_amd kernels need tensors on a HIP device, got {scores.device}")
-    s = scores.to(torch.float32).contiguous()
-    L = s.shape[-1]
-    assert L % seg_len == 0, (L, seg_len)
-    nseg = L // seg_len
-    lead = s.shape[:-1]
-    s2 = s.reshape(-1, L)
-    R = s2.shape[0]
-    idx = torch.empty((R, nseg * k), dtype=torch.int32, device=s.device)
-    if R and k:
-        with _on_device(s.device):
-            if seg_len <= 32768:
-                # chunks this short are selected by one workgroup each (topk_row_kernel): no workspace at all.  (Round 6: a fresh
-                # zero-filled 33 MB workspace per call was 11 us of ChunkPress's 128k step -- profiles/r06_rocprofv3_kernel_stats_chunk_snapkv128k.csv)
-                _check(lib().kvp_topk_select_segmented(_p(s2), R, nseg, int(seg_len), int(k), int(pos_base), 0, _p(idx), None, 0, _stream(s)),
-                       "kvp_topk_select_segmented")
-            else:
-                stream = torch.cuda.current_stream(s.device)
-                nws = max(int(lib().kvp_topk_segmented_workspace_bytes(R, nseg, seg_len, k)), 256)
-                ws = _cached_ws(("seg", s.device.index, stream.cuda_stream, R, nseg, int(seg_len)), nws, s.device)   # zeroed once, self-cleaning
-                try:
-                    _check(lib().kvp_topk_select_segmented(_p(s2), R, nseg, int(seg_len), int(k), int(pos_base), TOPK_WS_CLEAN, _p(idx), _p(ws),
-                                                           ws.numel(), _stream(s)), "kvp_topk_select_segmented")
-                except KvpressHipError:
-                    _drop_ws(ws)
-                    raise
-    return idx.reshape(*lead, nseg * k)
-
-
-def rerotate_keys_(keys_kept: torch.Tensor, idx: torch.Tensor, inv_freq: torch.Tensor) -> torch.Tensor:
-    """In place: re-rotate gathered keys [B,H,n,D] (kept at ascending positions idx [B,H,n]) to positions 0..n-1."""
-    _dev(keys_kept)
-    assert keys_kept.is_contiguous()
-    B, H, n, D = keys_kept.shape
-    idx = idx.to(torch.int32).contiguous()
-    assert idx.shape == (B, H, n)
-    inv = inv_freq.to(device=keys_kept.device, dtype=torch.float32).contiguous()
-    assert inv.numel() == D // 2
-    with _on_device(keys_kept.device):
-        _check(lib().kvp_rerotate_keys(_p(keys_kept), _DTYPES[keys_kept.dtype], B, H, n, D, _p(idx), _p(inv), _stream(keys_kept)),
-               "kvp_rerotate_keys")
-    return keys_kept
-
-
-_WS_BYTES: dict = {}
-
-
-def _ws_bytes(fn_name: str, *shape) -> int:
-    """kvp_*_workspace_bytes(shape), remembered per shape (a ctypes call per compress is measurable in the decode regime)."""
-    key = (fn_name,) + shape
-    n = _WS_BYTES.get(key)
-    if n is None:
-        if len(_WS_BYTES) > 256:
-            _WS_BYTES.clear()
-        n = _WS_BYTES[key] = int(getattr(lib(), fn_name)(*shape))
-    return n
-
-
-def _clean_ws(kind: str, shape: tuple, nbytes: int, like: torch.Tensor, stream_handle: Optional[int] = None) -> torch.Tensor:
-    """Zero-filled-once workspace of a fused compress call, one per (device, stream, call shape): the calls leave its
-    histogram region clean, so it is passed with KVP_TOPK_WS_CLEAN from then on."""
-    if stream_handle is None:
-        stream_handle = torch.cuda.current_stream(like.device).cuda_stream
-    key = (kind, like.device.index, stream_handle) + tuple(shape)
-    return _cached_ws(key, nbytes, like.device)
-
-
-def _cached_ws(key: tuple, nbytes: int, device) -> torch.Tensor:
-    """One zero-filled workspace per (calling thread, key): two Python threads never share one, even on the same stream."""
-    key = (threading.get_ident(),) + tuple(key)
-    with _TOPK_WS_LOCK:
-        ws = _TOPK_WS.get(key)
-        if ws is None:
-            if len(_TOPK_WS) > 64:
-                _TOPK_WS.clear()
-            ws = torch.zeros(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-            _TOPK_WS[key] = ws
-    return ws
-
-
-def _drop_ws(ws: torch.Tensor):
-    with _TOPK_WS_LOCK:
-        for key in [k for k, v in _TOPK_WS.items() if v is ws]:
-            del _TOPK_WS[key]
-
-
-def knorm_compress(keys: torch.Tensor, values: torch.Tensor, n_kept: int, order: int = ORDER_POSITION):
-    """KnormPress.compress in one library call: (K', V') contiguous [B,H,n_kept,D]; order = ORDER_SCORE stores the rows in descending
-    score order (the reference's layout)."""
-    keys = _rows_last_contig(_dev(keys))
-    values = _rows_last_contig(_dev(values))
-    assert keys.dtype == values.dtype and keys.shape == values.shape
-    B, H, S, D = keys.shape
-    n = int(n_kept)
-    ko = torch.empty((B, H, n, D), dtype=keys.dtype, device=keys.device)
-    vo = torch.empty_like(ko)
-    if n and B and H:
-        with _on_device(keys.device):
-            st = _stream(keys)
-            ws = _clean_ws("knorm", (B, H, S, n), _ws_bytes("kvp_knorm_compress_workspace_bytes", B, H, S, n), keys, st)
-            rc = lib().kvp_knorm_compress(_p(keys), _st(keys, 0), _st(keys, 1), _st(keys, 2), _p(values), _st(values, 0), _st(values, 1),
-                                          _st(values, 2), _DTYPES[keys.dtype], B, H, S, D, n, _p(ko), _p(vo), _p(ws), ws.numel(),
-                                          TOPK_WS_CLEAN | (int(order) & ORDER_SCORE), st)
-            if rc != 0:
-                _drop_ws(ws)
-            _check(rc, "kvp_knorm_compress")
-    return ko, vo
-
-
-def snapkv_compress_rope(q_pre: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, keys: torch.Tensor, values: torch.Tensor,
-                         kernel_size: int, n_kept: int, order: int = ORDER_POSITION):
-    """SnapKVPress.compress (attentions=None) in one library call from the pre-RoPE window queries; order = ORDER_SCORE stores the rows
-    in descending score order (window tokens first: the reference's layout)."""
-    keys = _rows_last_contig(_dev(keys))
-    values = _rows_last_contig(_dev(values))
-    q_pre = _rows_last_contig(_dev(q_pre))
-    dt = keys.dtype
-    assert values.dtype == dt and keys.shape == values.shape
-    if q_pre.dtype != dt:
-        q_pre = q_pre.to(dt)
-    cos = _rows_last_contig(_dev(cos.to(dt)))
-    sin = _rows_last_contig(_dev(sin.to(dt)))
-    B, Hq, W, D = q_pre.shape
-    Bk, Hkv, S, Dk = keys.shape
-    assert B == Bk and D == Dk and Hq % Hkv == 0, (q_pre.shape, keys.shape)
-    cos, sin = _window_tables(cos, sin, B, W, D)
-    n = int(n_kept)
-    ko = torch.empty((B, Hkv, n, D), dtype=dt, device=keys.device)
-    vo = torch.empty_like(ko)
-    if n:
-        with _on_device(keys.device):
-            st = _stream(keys)
-            ws = _clean_ws("snapkv", (B, Hq, Hkv, S, W, D, n), _ws_bytes("kvp_snapkv_compress_workspace_bytes", B, Hq, Hkv, S, W, D, n), keys, st)
-            rc = lib().kvp_snapkv_compress_rope(_p(q_pre), _st(q_pre, 0), _st(q_pre, 1), _st(q_pre, 2), _p(cos), _p(sin), _st(cos, 0),
-                                                _st(cos, 1), _p(keys), _st(keys, 0), _st(keys, 1), _st(keys, 2), _p(values),
-                                                _st(values, 0), _st(values, 1), _st(values, 2), _DTYPES[dt], B, Hq, Hkv, S, W, D,
-                                                int(kernel_size), n, _p(ko), _p(vo), _p(ws), ws.numel(), TOPK_WS_CLEAN | (int(order) & ORDER_SCORE), st)
-            if rc != 0:
-                _drop_ws(ws)
-            _check(rc, "kvp_snapkv_compress_rope")
-    return ko, vo
-
-
-def gather_kv(keys: torch.Tensor, values: torch.Tensor, idx: torch.Tensor):
-    """K'[b,h,j] = K[b,h,idx[b,h,j]] (and V'), contiguous [B,H,n,D] in the input dtype."""
-    keys = _rows_last_contig(_dev(keys))
-    values = _rows_last_contig(_dev(values))
-    assert keys.dtype == values.dtype and keys.shape == values.shape
-    B, H, S, D = keys.shape
-    idx = idx.to(torch.int32).contiguous()
-    n = idx.shape[-1]
-    assert idx.shape == (B, H, n)
-    ko = torch.empty((B, H, n, D), dtype=keys.dtype, device=keys.device)
-    vo = torch.empty((B, H, n, D), dtype=values.dtype, device=values.device)
-    if B * H * n:
-        with _on_device(keys.device):
-            _check(lib().kvp_gather_kv(_p(keys), _st(keys, 0), _st(keys, 1), _st(keys, 2),
-                                       _p(values), _st(values, 0), _st(values, 1), _st(values, 2), _DTYPES[keys.dtype],
-                                       B, H, S, D, _p(idx), n, _p(ko), _p(vo), _stream(keys)), "kvp_gather_kv")
-    return ko, vo
-
-
-def gather_kv_rerotate(keys: torch.Tensor, values: torch.Tensor, idx: torch.Tensor, inv_freq: torch.Tensor):
-    """gather_kv + rerotate_keys_ in one pass: K'[b,h,j] = K[b,h,idx[b,h,j]] re-rotated from position idx[b,h,j] to position j, V' the
-    plain gather (same bits as the two calls)."""
-    keys = _rows_last_contig(_dev(keys))
-    values = _rows_last_contig(_dev(values))
-    assert keys.dtype == values.dtype and keys.shape == values.shape
-    B, H, S, D = keys.shape
-    idx = idx.to(torch.int32).contiguous()
-    n = idx.shape[-1]
-    assert idx.shape == (B, H, n)
-    inv = inv_freq.to(device=keys.device, dtype=torch.float32).contiguous()
-    assert inv.numel() == D // 2
-    ko = torch.empty((B, H, n, D), dtype=keys.dtype, device=keys.device)
-    vo = torch.empty((B, H, n, D), dtype=values.dtype, device=values.device)
-    if B * H * n:
-        with _on_device(keys.device):
-            _check(lib().kvp_gather_kv_rerotate(_p(keys), _st(keys, 0), _st(keys, 1), _st(keys, 2),
-                                                _p(values), _st(values, 0), _st(values, 1), _st(values, 2), _DTYPES[keys.dtype],
-                                                B, H, S, D, _p(idx), n, _p(inv), _p(ko), _p(vo), _stream(keys)), "kvp_gather_kv_rerotate")
-    return ko, vo
-
-
-# ------------------------------------------------------------------------------------------------
+# ---- lab aids: include/kvpress_hip_lab.h (bench.py, tools/, the select's residency tests) -----------------------------------------------
 def clock_probe(device=None, spin_us: int = 20) -> torch.Tensor:
     """Enqueue a shader-clock probe on the current stream; returns a 1-element float32 device tensor (MHz) that is valid
     once the stream has run it."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     out = torch.zeros(1, dtype=torch.float32, device=dev)
     with _on_device(dev):
-        _check(lib().kvp_clock_probe(_p(out), int(spin_us), _stream(out)), "kvp_clock_probe")
+        _call("kvp_clock_probe", _p(out), int(spin_us), _stream(out))
     return out
 
 
@@ -862,12 +873,12 @@ def occupy_cus(blocks: int, threads: int, lds_bytes: int, spin_us: int, stream=N
     """TEST AID: enqueue `blocks` workgroups that hold `threads` threads + `lds_bytes` of LDS for `spin_us` microseconds on
     `stream` (default: the current one)."""
     st = stream if stream is not None else torch.cuda.current_stream()
-    _check(lib().kvp_occupy_cus(int(blocks), int(threads), int(lds_bytes), int(spin_us), c_void_p(st.cuda_stream)), "kvp_occupy_cus")
+    _call("kvp_occupy_cus", int(blocks), int(threads), int(lds_bytes), int(spin_us), c_void_p(st.cuda_stream))
 
 
 def prof_enable(on: bool) -> None:
     """Turn the library's per-kernel HIP-event timing on/off (clears previous records)."""
-    _check(lib().kvp_prof_enable(int(bool(on))), "kvp_prof_enable")
+    _call("kvp_prof_enable", int(bool(on)))
 
 
 def prof_records():
@@ -875,109 +886,11 @@ def prof_records():
     out = []
     name, ms = c_char_p(), c_float()
     for i in range(lib().kvp_prof_count()):
-        _check(lib().kvp_prof_get(i, ctypes.byref(name), ctypes.byref(ms)), "kvp_prof_get")
+        _call("kvp_prof_get", i, ctypes.byref(name), ctypes.byref(ms))
         out.append((name.value.decode(), float(ms.value)))
     return out
 
 
 def tuning_reload() -> None:
     """Make the library re-read its KVP_* tuning variables (they are read from the environment once and cached)."""
-    _check(lib().kvp_tuning_reload(), "kvp_tuning_reload")
-
-
-# ---- the Compactor family (non_causal_attention_press.py, leverage_press.py, compactor_press.py) --------------------------------------
-def ncattn_score(q_pre: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, keys: torch.Tensor, values: torch.Tensor, chunk_size: int,
-                 return_raw: bool = False):
-    """NonCausalAttnPress scores (non_causal_attention_press.py:95-122): z-scores [B,Hkv,S] float32 from the PRE-RoPE queries
-    [B,Hq,S,D], the rotary tables of the same S positions [1 or B, S, D], keys and values [B,Hkv,S,D]; with ``return_raw`` also the
-    scores before the z-score."""
-    keys = _rows_last_contig(_dev(keys))
-    values = _rows_last_contig(_dev(values))
-    q_pre = _rows_last_contig(_dev(q_pre))
-    dt = keys.dtype
-    if q_pre.dtype != dt:
-        q_pre = q_pre.to(dt)
-    if values.dtype != dt:
-        values = values.to(dt)
-    B, Hq, S, D = q_pre.shape
-    Bk, Hkv, Sk, Dk = keys.shape
-    assert B == Bk and S == Sk and D == Dk and tuple(values.shape[:3]) == (B, Hkv, S) and values.shape[3] == D, (q_pre.shape, keys.shape, values.shape)
-    if Hq % Hkv != 0:
-        raise KvpressHipError(f"kvp_ncattn_score: Hq % Hkv != 0 ({Hq}, {Hkv})")
-    cos = _rows_last_contig(_dev(cos.to(dt)))
-    sin = _rows_last_contig(_dev(sin.to(dt)))
-    assert cos.shape == sin.shape and cos.shape[-1] == D and cos.shape[-2] == S and cos.shape[0] in (1, B), (cos.shape, q_pre.shape)
-    if sin.stride() != cos.stride():
-        cos, sin = cos.contiguous(), sin.contiguous()
-    raw = torch.empty((B, Hkv, S), dtype=torch.float32, device=keys.device) if return_raw else None
-    z = torch.empty((B, Hkv, S), dtype=torch.float32, device=keys.device)
-    with _on_device(keys.device):
-        ws = _ws(lib().kvp_ncattn_workspace_bytes(B, Hkv, S), keys)
-        _check(lib().kvp_ncattn_score(_p(q_pre), _st(q_pre, 0), _st(q_pre, 1), _st(q_pre, 2), _p(cos), _p(sin), _st(cos, 0), _st(cos, 1),
-                                      _p(keys), _st(keys, 0), _st(keys, 1), _st(keys, 2), _p(values), _st(values, 0), _st(values, 1),
-                                      _st(values, 2), _DTYPES[dt], B, Hq, Hkv, S, D, int(chunk_size), _p(raw), _p(z), _p(ws), ws.numel(),
-                                      _stream(keys)), "kvp_ncattn_score")
-    return (z, raw) if return_raw else z
-
-
-def leverage_score(keys_pre: torch.Tensor, phi: torch.Tensor, return_raw: bool = False):
-    """LeverageScorePress scores (leverage_press.py:59-110): z-scores [B,H,S] float32 from the PRE-RoPE keys [B,H,S,D] and the
-    Gaussian sketch phi [B,H,D,k] (drawn by the caller, leverage_press.py:68-75).  Synchronises the stream to check the Cholesky
-    factorisation, as the reference does; raises KvpressHipError("... Cholesky failed after 5 tries ...") like its RuntimeError."""
-    k = _rows_last_contig(_dev(keys_pre))
-    phi = _rows_last_contig(_dev(phi))
-    if phi.dtype != k.dtype:
-        phi = phi.to(k.dtype)
-    B, H, S, D = k.shape
-    assert tuple(phi.shape[:3]) == (B, H, D), (phi.shape, k.shape)
-    ks = phi.shape[3]
-    raw = torch.empty((B, H, S), dtype=torch.float32, device=k.device) if return_raw else None
-    z = torch.empty((B, H, S), dtype=torch.float32, device=k.device)
-    with _on_device(k.device):
-        ws = _ws(lib().kvp_leverage_workspace_bytes(B, H, S, D, ks), k)
-        _check(lib().kvp_leverage_score(_p(k), _st(k, 0), _st(k, 1), _st(k, 2), _p(phi), _st(phi, 0), _st(phi, 1), _st(phi, 2),
-                                        _DTYPES[k.dtype], B, H, S, D, ks, _p(raw), _p(z), _p(ws), ws.numel(), _stream(k)), "kvp_leverage_score")
-        _check(lib().kvp_leverage_status(_p(ws), B, H, S, D, ks, _stream(k)), "kvp_leverage_score")
-    return (z, raw) if return_raw else z
-
-
-def compactor_combine(z_lev: torch.Tensor, z_attn: torch.Tensor, sink_start: int, sink_end: int, blending: float) -> torch.Tensor:
-    """blending * z_lev + z_attn, padded with sink_start / sink_end positions holding the global max (compactor_press.py:119-122)."""
-    z_lev = _dev(z_lev).contiguous()
-    z_attn = _dev(z_attn).contiguous()
-    assert z_lev.shape == z_attn.shape and z_lev.dtype == torch.float32 and z_attn.dtype == torch.float32, (z_lev.shape, z_attn.shape)
-    B, H, Si = z_lev.shape
-    out = torch.empty((B, H, Si + sink_start + sink_end), dtype=torch.float32, device=z_lev.device)
-    with _on_device(z_lev.device):
-        ws = _ws(lib().kvp_compactor_combine_workspace_bytes(), z_lev)
-        _check(lib().kvp_compactor_combine(_p(z_lev), _p(z_attn), B, H, Si, int(sink_start), int(sink_end), float(blending), _p(out), _p(ws),
-                                           ws.numel(), _stream(z_lev)), "kvp_compactor_combine")
-    return out
-
-
-# ---- MergingPress (merging_press.py:99-177) ---------------------------------------------------------------------------------------------
-def merge_values_(keys: torch.Tensor, values: torch.Tensor, kept_idx: torch.Tensor, k_out: torch.Tensor, v_out: torch.Tensor,
-                  threshold: float, fraction: float, target: Optional[torch.Tensor] = None, max_sim: Optional[torch.Tensor] = None):
-    """MergingPress.merge after the select and the gather: folds every evicted token's value (keys / values [B,H,S,D], evicted = not in
-    the int32 kept_idx [B,H,n_kept]) into its most cosine-similar kept row, IN PLACE in v_out (the contiguous gathered V'; k_out is the
-    gathered K').  ``target`` (int32) / ``max_sim`` (float32) [B,H,S-n_kept], if given, receive the argmax and its cosine.  Returns v_out."""
-    keys = _rows_last_contig(_dev(keys))
-    values = _rows_last_contig(_dev(values))
-    dt = keys.dtype
-    B, H, S, D = keys.shape
-    assert values.dtype == dt and tuple(values.shape) == (B, H, S, D), (keys.shape, values.shape)
-    n = kept_idx.shape[-1]
-    assert tuple(kept_idx.shape) == (B, H, n) and kept_idx.dtype == torch.int32 and kept_idx.is_contiguous(), (kept_idx.shape, kept_idx.dtype)
-    for t in (k_out, v_out):
-        assert t.dtype == dt and tuple(t.shape) == (B, H, n, D) and t.is_contiguous() and t.device == keys.device, (t.shape, t.dtype)
-    for t, tdt in ((target, torch.int32), (max_sim, torch.float32)):
-        if t is not None:
-            assert t.dtype == tdt and tuple(t.shape) == (B, H, S - n) and t.is_contiguous(), (t.shape, t.dtype)
-    if n == 0 or n == S:
-        return v_out
-    with _on_device(keys.device):
-        ws = _ws(lib().kvp_merge_workspace_bytes(B, H, S, n, D), keys)
-        _check(lib().kvp_merge_values(_p(keys), _st(keys, 0), _st(keys, 1), _st(keys, 2), _p(values), _st(values, 0), _st(values, 1),
-                                      _st(values, 2), _p(kept_idx), _p(k_out), _p(v_out), _DTYPES[dt], B, H, S, n, D, float(threshold),
-                                      float(fraction), _p(ws), ws.numel(), _p(target), _p(max_sim), _stream(keys)), "kvp_merge_values")
-    return v_out
+    _call("kvp_tuning_reload")

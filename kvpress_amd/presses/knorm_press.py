@@ -33,5 +33,4 @@ class KnormPress(ScorerPress):
             return keys, values
         if type(self).score is not KnormPress.score:
             return super().compress(module, hidden_states, keys, values, attentions, kwargs)
-        order = _native.ORDER_SCORE if self.kept_order == "score" else _native.ORDER_POSITION   # "score": the reference's row order
-        return _native.knorm_compress(keys, values, self.n_kept(module, keys.shape[2]), order)
+        return _native.knorm_compress(keys, values, self.n_kept(module, keys.shape[2]), self.library_order())

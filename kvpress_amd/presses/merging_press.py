@@ -61,8 +61,7 @@ class MergingPress(BasePress):
         scores = self.press.score(module, hidden_states, keys, values, attentions, kwargs)
         k_len = keys.shape[2]
         n_kept = int(k_len * (1 - self.press.compression_ratio))
-        order = _native.ORDER_SCORE if self.press.kept_order == "score" else _native.ORDER_POSITION
-        indices = _native.topk_select(scores, n_kept, order)                  # int32 [B, H, n_kept]
+        indices = _native.topk_select(scores, n_kept, self.press.library_order())   # int32 [B, H, n_kept]
         k_out, v_out = _native.gather_kv(keys, values, indices)               # new contiguous tensors: the inputs stay untouched
         if 0 < n_kept < k_len:                                                # merging_press.py:120-121
             _native.merge_values_(keys, values, indices, k_out, v_out, self.similarity_threshold, self.merge_fraction)

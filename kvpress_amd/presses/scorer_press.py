@@ -115,12 +115,15 @@ class ScorerPress(BasePress):
         (scorer_press.py:93-94); presses with per-layer budgets override this."""
         return int(k_len * (1 - self.compression_ratio))
 
+    def library_order(self) -> int:
+        """``kept_order`` as the library's order constant ("score": the reference's row order)."""
+        return _native.ORDER_SCORE if self.kept_order == "score" else _native.ORDER_POSITION
+
     def compress(self, module: nn.Module, hidden_states: torch.Tensor, keys: torch.Tensor, values: torch.Tensor,
                  attentions: torch.Tensor, kwargs: dict) -> tuple[torch.Tensor, torch.Tensor]:
         if self.compression_ratio == 0:
             return keys, values
 
         scores = self.score(module, hidden_states, keys, values, attentions, kwargs)
-        order = _native.ORDER_SCORE if self.kept_order == "score" else _native.ORDER_POSITION
-        indices = _native.topk_select(scores, self.n_kept(module, keys.shape[2]), order)  # int32 [B,H,n_kept]
+        indices = _native.topk_select(scores, self.n_kept(module, keys.shape[2]), self.library_order())  # int32 [B,H,n_kept]
         return _native.gather_kv(keys, values, indices)                             # contiguous [B,H,n_kept,D]

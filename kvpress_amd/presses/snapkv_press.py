@@ -43,24 +43,31 @@ class SnapKVPress(ScorerPress):
         cos, sin = cos[:, -window_size:], sin[:, -window_size:]
         return (query_states * cos.unsqueeze(1)) + (_rotate_half(query_states) * sin.unsqueeze(1))
 
-    def score(self, module: nn.Module, hidden_states: torch.Tensor, keys: torch.Tensor, values: torch.Tensor,
-              attentions: torch.Tensor, kwargs) -> torch.Tensor:
-        k_len = keys.shape[2]
+    def _window_inputs(self, module: nn.Module, hidden_states: torch.Tensor, attentions, kwargs):
+        """What the library scores the window from, unless ``attentions`` are given (None): (True, (hidden states of the window,
+        q_proj weight, cos, sin)) where it projects the window itself, else (False, (pre-RoPE window queries, cos, sin))."""
         assert (
             hidden_states.shape[1] > self.window_size
         ), f"Query length {hidden_states.shape[1]} should be greater than the window size {self.window_size}"
-
         if attentions is not None:
-            attn = attentions[..., -self.window_size:, : -self.window_size]  # snapkv_press.py:88-89
-            return _native.snapkv_score_from_attn(attn, keys.shape[1], k_len, self.kernel_size)
+            return None
         cos, sin = kwargs["position_embeddings"]
         cos, sin = cos[:, -self.window_size:], sin[:, -self.window_size:]
         if _native.qproj_rope_supported(module, hidden_states, self.window_size):
             # plain bf16 / f16 nn.Linear q_proj: projection of the last W tokens + RoPE in one library kernel
-            return _native.snapkv_score_hidden(hidden_states[:, -self.window_size:], module.q_proj.weight, cos, sin, keys, self.kernel_size)
+            return True, (hidden_states[:, -self.window_size:], module.q_proj.weight, cos, sin)
         # otherwise q_proj stays the model's own call (quantised / LoRA / q_norm ...); RoPE + the rest in the library
-        q_pre = get_prerope_query_states(module, hidden_states[:, -self.window_size:])
-        return _native.snapkv_score_rope(q_pre, cos, sin, keys, self.kernel_size)
+        return False, (get_prerope_query_states(module, hidden_states[:, -self.window_size:]), cos, sin)
+
+    def score(self, module: nn.Module, hidden_states: torch.Tensor, keys: torch.Tensor, values: torch.Tensor,
+              attentions: torch.Tensor, kwargs) -> torch.Tensor:
+        window = self._window_inputs(module, hidden_states, attentions, kwargs)
+        if window is None:
+            attn = attentions[..., -self.window_size:, : -self.window_size]  # snapkv_press.py:88-89
+            return _native.snapkv_score_from_attn(attn, keys.shape[1], keys.shape[2], self.kernel_size)
+        from_hidden, args = window
+        score = _native.snapkv_score_hidden if from_hidden else _native.snapkv_score_rope
+        return score(*args, keys, self.kernel_size)
 
     def compress(self, module: nn.Module, hidden_states: torch.Tensor, keys: torch.Tensor, values: torch.Tensor,
                  attentions: torch.Tensor, kwargs: dict) -> tuple[torch.Tensor, torch.Tensor]:
@@ -72,15 +79,6 @@ class SnapKVPress(ScorerPress):
             return keys, values
         if attentions is not None or type(self).score is not SnapKVPress.score:
             return super().compress(module, hidden_states, keys, values, attentions, kwargs)
-        order = _native.ORDER_SCORE if self.kept_order == "score" else _native.ORDER_POSITION   # "score": the reference's row order
-        assert (
-            hidden_states.shape[1] > self.window_size
-        ), f"Query length {hidden_states.shape[1]} should be greater than the window size {self.window_size}"
-        cos, sin = kwargs["position_embeddings"]
-        cos, sin = cos[:, -self.window_size:], sin[:, -self.window_size:]
-        n_kept = self.n_kept(module, keys.shape[2])
-        if _native.qproj_rope_supported(module, hidden_states, self.window_size):
-            return _native.snapkv_compress_hidden(hidden_states[:, -self.window_size:], module.q_proj.weight, cos, sin, keys, values,
-                                                  self.kernel_size, n_kept, order)
-        q_pre = get_prerope_query_states(module, hidden_states[:, -self.window_size:])
-        return _native.snapkv_compress_rope(q_pre, cos, sin, keys, values, self.kernel_size, n_kept, order)
+        from_hidden, args = self._window_inputs(module, hidden_states, None, kwargs)
+        compress = _native.snapkv_compress_hidden if from_hidden else _native.snapkv_compress_rope
+        return compress(*args, keys, values, self.kernel_size, self.n_kept(module, keys.shape[2]), self.library_order())

@@ -140,12 +140,76 @@ def test_no_hand_written_prototypes_of_other_files_functions():
     assert not bad, f"prototypes of functions defined in another .hip (declare them in kvp_host.h): {bad}"
 
 
+C_TYPES = {"void": None, "char": ctypes.c_char, "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
+           "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def _c_type(text):
+    """a C type as the headers spell it -> (number of `*`, ctypes type of the value / of what is pointed to; None for void).
+    An unknown type fails the test instead of being skipped."""
+    words = re.sub(r"\bconst\b", " ", text).replace("*", " * ").split()
+    depth, base = words.count("*"), [w for w in words if w != "*"]
+    if base == ["kvp_stream_t"]:      # typedef void* kvp_stream_t
+        depth, base = depth + 1, ["void"]
+    assert len(base) == 1 and base[0] in C_TYPES and (depth or base[0] != "void"), f"unknown C type {text!r}"
+    return depth, C_TYPES[base[0]]
+
+
+def declared_prototypes(headers=("kvpress_hip.h",)):
+    """{name: (return type, [parameter types])} of every kvp_* prototype, each type as _c_type gives it"""
+    protos = {}
+    for h in headers:
+        text = open(os.path.join(ROOT, "include", h)).read()
+        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+        for ret, name, params in re.findall(r"^([A-Za-z_][\w \t*]*?)\b(kvp_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text, flags=re.M):
+            params = [p.strip() for p in params.split(",")]
+            if params == ["void"]:
+                params = []
+            # a parameter is `type name`: the name is the last identifier
+            protos[name] = (_c_type(ret), [_c_type(re.fullmatch(r"(.*?)\b[A-Za-z_]\w*", p, flags=re.S).group(1)) for p in params])
+    return protos
+
+
+def _binds(ctype, c_type):
+    """does the ctypes type of a signature table bind the C type?  Values by exact type; any pointer (kvp_stream_t is one) as c_void_p,
+    or as a typed pointer whose pointee matches (c_char_p for `const char*`, POINTER(c_float) for `float*`)."""
+    depth, base = c_type
+    if depth == 0:
+        return ctype is base
+    if ctype is ctypes.c_void_p:
+        return True
+    if ctype is ctypes.c_char_p:
+        return (depth, base) == (1, ctypes.c_char)
+    pointee = getattr(ctype, "_type_", None)
+    return isinstance(pointee, type) and _binds(pointee, (depth - 1, base))
+
+
+def signature_mismatches(table, protos):
+    bad = []
+    for name, (res, args) in table.items():
+        ret, params = protos[name]
+        if not _binds(res, ret):
+            bad.append(f"{name}: returns {ret}, bound as {res.__name__}")
+        if len(args) != len(params):
+            bad.append(f"{name}: {len(params)} parameters, bound with {len(args)}")
+        bad += [f"{name}: parameter {i} is {p}, bound as {a.__name__}" for i, (a, p) in enumerate(zip(args, params)) if not _binds(a, p)]
+    return bad
+
+
 def test_binding_covers_header(lib):
+    """the three signature tables of the binding against the three headers: the same names, and per entry the return type and the
+    arity, order and type of the parameters (a c_int for an int64_t, or a c_float for a double, shifts every later argument)"""
     from kvpress_amd import _native
 
     assert sorted(_native.SIGNATURES) == declared_symbols()
     assert sorted(_native.LAB_SIGNATURES) == declared_symbols(("kvpress_hip_lab.h",))
     assert sorted(_native.CONTRIB_SIGNATURES) == declared_symbols(("kvpress_hip_extra.h",))
+    for table, header in ((_native.SIGNATURES, "kvpress_hip.h"), (_native.LAB_SIGNATURES, "kvpress_hip_lab.h"),
+                          (_native.CONTRIB_SIGNATURES, "kvpress_hip_extra.h")):
+        protos = declared_prototypes((header,))
+        assert sorted(protos) == declared_symbols((header,))     # the prototype scan sees every entry the name scan sees
+        bad = signature_mismatches(table, protos)
+        assert not bad, f"_native's table disagrees with include/{header}: {bad}"
 
 
 def test_version_and_errors(lib):
