@@ -10,13 +10,9 @@
 #include <cstdlib>
 #include <vector>
 
-#include "kvp_common.h"
+#include "kvp_mfma.h"
 
 namespace {
-
-typedef __bf16 cpt_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 cpt_f16x8 __attribute__((ext_vector_type(8)));
-typedef float cpt_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int NC_THREADS = 512;   // MFMA path: 8 waves
 constexpr int NC_WAVES = NC_THREADS / 64;
@@ -24,32 +20,6 @@ constexpr int GEN_THREADS = 256;  // generic paths
 constexpr int ZS_BLOCKS = 256;    // partial sums of the global z-score
 constexpr int LV_TILE = 32;       // tokens per leverage tile
 constexpr int LV_THREADS = 256;
-
-template <int DT> __device__ __forceinline__ uint16_t to_bits(float x);
-template <> __device__ __forceinline__ uint16_t to_bits<KVP_BF16>(float x) { return (uint16_t)(__float_as_uint(round_dt<KVP_BF16>(x)) >> 16); }
-template <> __device__ __forceinline__ uint16_t to_bits<KVP_F16>(float x) {
-    const _Float16 h = (_Float16)x;
-    return __builtin_bit_cast(uint16_t, h);
-}
-
-template <int DT> __device__ __forceinline__ cpt_f32x16 mfma32(const uint4& a, const uint4& b, const cpt_f32x16& c);
-template <> __device__ __forceinline__ cpt_f32x16 mfma32<KVP_BF16>(const uint4& a, const uint4& b, const cpt_f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cpt_bf16x8, a), __builtin_bit_cast(cpt_bf16x8, b), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ cpt_f32x16 mfma32<KVP_F16>(const uint4& a, const uint4& b, const cpt_f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(cpt_f16x8, a), __builtin_bit_cast(cpt_f16x8, b), c, 0, 0, 0);
-}
-
-// an MFMA result rounded to the model dtype (the matmul's output rounding) WITHOUT inline asm: round_dt's asm reads the accumulator
-// registers with no wait states after the MFMA that writes them (the compiler pads hazards around its own instructions, not inside
-// asm), which read partly written accumulators on hardware
-template <int DT> __device__ __forceinline__ float round_acc(float x);
-template <> __device__ __forceinline__ float round_acc<KVP_F16>(float x) { return (float)(_Float16)x; }
-template <> __device__ __forceinline__ float round_acc<KVP_BF16>(float x) {
-    const uint32_t u = __float_as_uint(x);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return __uint_as_float((u | 0x00400000u) & 0xFFFF0000u);
-    return __uint_as_float((u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u);
-}
 
 // block-wide sum / max of one value per thread, fixed order (wave butterflies, then the waves in index order); every thread gets it
 template <int NT> __device__ __forceinline__ float block_sum(float v, float* red) {
@@ -65,7 +35,7 @@ template <int NT> __device__ __forceinline__ float block_sum(float v, float* red
 }
 template <int NT> __device__ __forceinline__ double block_sum_d(double v, double* red) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);   // (written out: through a wave_sum call the scheduler moves the wave-index shift below)
     const int w = threadIdx.x >> 6;
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[w] = v;
@@ -118,7 +88,7 @@ __global__ __launch_bounds__(NC_THREADS) void ncattn_mfma_kernel(
     int Hkv, int G, int S, int C, float* __restrict__ tmp) {
     using G_ = NcGeo<D>;
     using T = typename Elem<DT>::T;
-    __shared__ __attribute__((aligned(16))) uint16_t qs[G_::QB * D];
+    __shared__ __attribute__((aligned(16))) typename Elem<DT>::T qs[G_::QB * D];
     __shared__ float st_m[G_::QB];
     __shared__ float st_il[G_::QB];
     __shared__ float part[16 * 32];
@@ -136,7 +106,7 @@ __global__ __launch_bounds__(NC_THREADS) void ncattn_mfma_kernel(
     const T* cbase = cosp + (int64_t)b * cs_sb + (int64_t)c0 * cs_ss;
     const T* sbase = sinp + (int64_t)b * cs_sb + (int64_t)c0 * cs_ss;
 
-    cpt_f32x16 colacc[2];
+    f32x16 colacc[2];
 #pragma unroll
     for (int p = 0; p < 2; ++p)
 #pragma unroll
@@ -161,8 +131,8 @@ __global__ __launch_bounds__(NC_THREADS) void ncattn_mfma_kernel(
                     hi = rope_elem<DT>(q1, Elem<DT>::ld(cr + d + D / 2), q0, Elem<DT>::ld(sr + d + D / 2));
                 }
                 const int d2 = d + D / 2;
-                qs[r * D + G_::swz(r, d / 8) * 8 + (d & 7)] = to_bits<DT>(lo);
-                qs[r * D + G_::swz(r, d2 / 8) * 8 + (d2 & 7)] = to_bits<DT>(hi);
+                qs[r * D + G_::swz(r, d / 8) * 8 + (d & 7)] = to_dt<DT>(lo);
+                qs[r * D + G_::swz(r, d2 / 8) * 8 + (d2 & 7)] = to_dt<DT>(hi);
             }
             __syncthreads();
             // pass 1: row max and 1 / row sum
@@ -174,14 +144,14 @@ __global__ __launch_bounds__(NC_THREADS) void ncattn_mfma_kernel(
                 float m = -INFINITY, l = 0.f;
                 for (int kt = 0; kt < nkt; ++kt) {
                     const int key = kt * 32 + r32;
-                    cpt_f32x16 acc;
+                    f32x16 acc;
 #pragma unroll
                     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll
                     for (int s = 0; s < G_::KS; ++s) {
                         uint4 ak = make_uint4(0, 0, 0, 0);
                         if (key < nvalid) ak = *reinterpret_cast<const uint4*>(kb + key * k_ss + 16 * s + 8 * h);
-                        acc = mfma32<DT>(ak, bq[s], acc);
+                        acc = mma32<DT>(ak, bq[s], acc);
                     }
                     float x[16];
                     float tm = -INFINITY;
@@ -223,13 +193,13 @@ __global__ __launch_bounds__(NC_THREADS) void ncattn_mfma_kernel(
                     }
                     for (int qt = qsub; qt < nq / 32; qt += R) {
                         const int row = qt * 32 + r32;
-                        cpt_f32x16 acc;
+                        f32x16 acc;
 #pragma unroll
                         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll
                         for (int s = 0; s < G_::KS; ++s) {
                             const uint4 bq = *reinterpret_cast<const uint4*>(&qs[row * D + G_::swz(row, 2 * s + h) * 8]);
-                            acc = mfma32<DT>(ak[s], bq, acc);
+                            acc = mma32<DT>(ak[s], bq, acc);
                         }
                         const float mq = st_m[row], il = st_il[row];
 #pragma unroll
@@ -639,7 +609,7 @@ __global__ __launch_bounds__(GEN_THREADS) void cpt_blend_kernel(const float* __r
         m = cpt_nanmax(m, x);
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = cpt_nanmax(m, __shfl_xor(m, o));
+    for (int o = 32; o > 0; o >>= 1) m = cpt_nanmax(m, __shfl_xor(m, o));   // (written out, as block_sum_d's ladder: a shared butterfly changes the code around it)
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -227,11 +227,7 @@ __global__ __launch_bounds__(EVF_THREADS) void ea_vnorm_finalize_kernel(const ty
         const uint32_t row = row0 + wv;
         float m = KVP_NEG_INF, z = 0.f;
         for (uint32_t j = lane; j < nblk; j += 64) softmax_merge(m, z, part_m[(size_t)row * nblk + j], part_z[(size_t)row * nblk + j]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float m2 = __shfl_xor(m, o), z2 = __shfl_xor(z, o);
-            softmax_merge(m, z, m2, z2);
-        }
+        wave_softmax_merge(m, z);
         if (lane == 0) ag[wv] = m + log2f(z);
     }
     __syncthreads();

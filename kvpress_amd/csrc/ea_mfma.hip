@@ -12,45 +12,16 @@
 //     ~2^-17 relative), then a row-dot with K read back in the C layout (ds_read_b64 from the swizzled tile).
 //     (k^T A k depends only on the symmetric part of A, so feeding rows of cov as the "columns" is exact.)
 #include "ea_internal.h"
+#include "kvp_mfma.h"
 #include "softmax_stats.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int EM_THREADS = 256;
 constexpr int EM_TILE = 64;    // rows per LDS tile
 constexpr int EM_ROWB = 256;   // D = 128, 2-byte elements
 constexpr int EM_TILEB = EM_TILE * EM_ROWB;
 
-template <int DT> __device__ __forceinline__ f32x16 mma32(const uint4& a, const uint4& b, f32x16 c);
-template <> __device__ __forceinline__ f32x16 mma32<KVP_BF16>(const uint4& a, const uint4& b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ f32x16 mma32<KVP_F16>(const uint4& a, const uint4& b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-// two floats -> one dword of 16-bit values (round to nearest even), low half = a
-template <int DT> __device__ __forceinline__ uint32_t pack2(float a, float b);
-template <> __device__ __forceinline__ uint32_t pack2<KVP_BF16>(float a, float b) {
-    uint32_t r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-template <> __device__ __forceinline__ uint32_t pack2<KVP_F16>(float a, float b) {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    h2 p = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(uint32_t, p);
-}
-template <int DT> __device__ __forceinline__ float lo16(uint32_t w);
-template <int DT> __device__ __forceinline__ float hi16(uint32_t w);
-template <> __device__ __forceinline__ float lo16<KVP_BF16>(uint32_t w) { return __uint_as_float(w << 16); }
-template <> __device__ __forceinline__ float hi16<KVP_BF16>(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }
-template <> __device__ __forceinline__ float lo16<KVP_F16>(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFFu)); }
-template <> __device__ __forceinline__ float hi16<KVP_F16>(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)); }
 template <int DT> __device__ __forceinline__ uint32_t one16();
 template <> __device__ __forceinline__ uint32_t one16<KVP_BF16>() { return 0x3F80u; }
 template <> __device__ __forceinline__ uint32_t one16<KVP_F16>() { return 0x3C00u; }
@@ -112,7 +83,7 @@ __global__ __launch_bounds__(EM_THREADS, ET_OCC) void ea_qstats_tr_kernel(QstatA
     const uint32_t ntiles = (rend - rbeg + EM_TILE - 1) / EM_TILE;
 
     // ---- LDS-DMA: request j (0..3) of a tile moves rows 16 j + 4 wv + g; lane slot i16 fetches chunk i16 ^ (g << 2) (row & 3 == g)
-    const uint32_t ldsbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
+    const uint32_t ldsbase = KVP_LDS_ADDR(lds);
     const uint32_t gchunk = i16 ^ (g << 2);
     // byte offset of this lane's 16-byte chunk inside the head's row (quarters: chunks 0 .. 7 lie in quarter QA, 8 .. 15 in quarter QB of a 512-byte row)
     const uint32_t gch = a.quarters ? (gchunk < 8 ? EQ_QA[qpair] * 128 + gchunk * 16 : EQ_QB[qpair] * 128 + (gchunk - 8) * 16) : gchunk << 4;
@@ -128,16 +99,8 @@ __global__ __launch_bounds__(EM_THREADS, ET_OCC) void ea_qstats_tr_kernel(QstatA
             const uint32_t row = min(row0 + 16 * j + 4 * wv + g, a.Sq - 1);   // rows past the end are zeroed in LDS below
             const char* gp = base + (int64_t)row * row_bytes + gch;
             const uint32_t la = __builtin_amdgcn_readfirstlane(ldsbase + buf * EM_TILEB + (16 * j + 4 * wv) * EM_ROWB);
-            if (a.nch == 16) {
-                if (a.nt) asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off nt" ::"s"(la), "v"(gp) : "memory");
-                else asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(la), "v"(gp) : "memory");
-            } else {   // (every wave has lanes with a chunk: all waves issue all requests, the vmcnt bookkeeping below holds)
-                asm volatile("s_mov_b32 m0, %0" ::"s"(la) : "memory");
-                if (has_chunk) {
-                    if (a.nt) asm volatile("global_load_lds_dwordx4 %0, off nt" ::"v"(gp) : "memory");
-                    else asm volatile("global_load_lds_dwordx4 %0, off" ::"v"(gp) : "memory");
-                }
-            }
+            if (a.nch == 16) lds_dma16(la, gp, a.nt);
+            else lds_dma16_if(has_chunk, la, gp, a.nt);   // (every wave has lanes with a chunk: all waves issue all requests, the vmcnt bookkeeping below holds)
         }
     };
 #pragma unroll
@@ -158,7 +121,7 @@ __global__ __launch_bounds__(EM_THREADS, ET_OCC) void ea_qstats_tr_kernel(QstatA
 #pragma unroll
     for (int r = 0; r < 16; ++r) accs[r] = 0.f;
 
-    __builtin_amdgcn_s_waitcnt(0x0F70 | (4 * (ET_NBUF - 2)));   // tile 0 landed (this wave's part)
+    dma_wait<4 * (ET_NBUF - 2)>();   // tile 0 landed (this wave's part)
     __syncthreads();
     uint32_t bc = 0;
     for (uint32_t t = 0; t < ntiles; ++t) {
@@ -187,11 +150,11 @@ __global__ __launch_bounds__(EM_THREADS, ET_OCC) void ea_qstats_tr_kernel(QstatA
             accs = mma32<DT>(F[0], vone, accs);                                   // C[own dim][*] = sum over the 16 tokens
         }
         __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(0x0070 | (4 * (ET_NBUF - 2)));   // lgkmcnt(0) + tile t+1 landed
+        dma_wait<4 * (ET_NBUF - 2), true>();   // every LDS read done + tile t+1 landed
         __syncthreads();
         bc = (bc + 1) % ET_NBUF;
     }
-    __builtin_amdgcn_s_waitcnt(0x0F70);
+    dma_wait<0>();
 
     float* s2 = a.s2 + ((size_t)bh * a.nchunk + chunk) * 128 * 128;
 #pragma unroll
@@ -419,7 +382,7 @@ __global__ __launch_bounds__(EM_THREADS, 2) void ea_logits_mfma_kernel(EaArgs a,
 
     // K tiles travel HBM / L2 -> LDS by LDS-DMA (no staging registers, no ds_write): request j of a tile moves rows 16 j + 4 wv + g (g = lane
     // / 16), lane slot i16 fetches the 16-byte chunk i16 ^ (row & 15) -- the XOR swizzle of frag16 / krows applied on the global side.
-    const uint32_t ldsbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
+    const uint32_t ldsbase = KVP_LDS_ADDR(lds);
     const uint32_t dg = lane >> 4, di16 = lane & 15;
     auto request_tile = [&](uint32_t row0, uint32_t buf_off) {
 #pragma unroll
@@ -427,14 +390,13 @@ __global__ __launch_bounds__(EM_THREADS, 2) void ea_logits_mfma_kernel(EaArgs a,
             const uint32_t trow = 16 * j + 4 * wv + dg;
             const uint32_t r = min(row0 + trow, a.Sp - 1);   // rows past the end: any valid row (masked in the fold)
             const char* gp = kb + (int64_t)r * row_bytes + ((di16 ^ (trow & 15)) << 4);
-            const uint32_t la = __builtin_amdgcn_readfirstlane(ldsbase + buf_off + (16 * j + 4 * wv) * EM_ROWB);
-            asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(la), "v"(gp) : "memory");
+            lds_dma16(__builtin_amdgcn_readfirstlane(ldsbase + buf_off + (16 * j + 4 * wv) * EM_ROWB), gp);
         }
     };
     unsigned char* bufc = lds;
     unsigned char* bufn = lds + EL_TILEB;
     request_tile(kbeg, 0);
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this wave's part of tile 0 has landed
+    dma_wait<0>();   // vmcnt(0): this wave's part of tile 0 has landed
     __syncthreads();
     uint4 kfa[8], kfb[8];
     // Software pipeline over the 32-key sub-tiles, across tile boundaries: the chain of sub-tile s runs beside the row-dot of sub-tile
@@ -490,7 +452,7 @@ __global__ __launch_bounds__(EM_THREADS, 2) void ea_logits_mfma_kernel(EaArgs a,
         rowdot(kr0, 2, acc0, redw);
         EL_GROUP(4)
         __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): tile t + 1 has landed (this wave's part; the barrier covers the others)
+        dma_wait<0>();   // vmcnt(0): tile t + 1 has landed (this wave's part; the barrier covers the others)
         __syncthreads();
         unsigned char* tmp = bufc; bufc = bufn; bufn = tmp;
         if (t > 0) fold(t - 1, rprev);
@@ -500,7 +462,9 @@ __global__ __launch_bounds__(EM_THREADS, 2) void ea_logits_mfma_kernel(EaArgs a,
     rowdot(kr1, 3, acc1, red[rprev][2 * wv]);   // the last tile's last row-dot
     __syncthreads();
     fold(ntiles - 1, rprev);
-    // every thread owns keys: merge inside each wave, then across the four through LDS
+    // every thread owns keys: merge inside each wave, then across the four through LDS.  (The butterfly is softmax_stats.h's
+    // wave_softmax_merge written out, here and in the three kernels below: called on m_run / z_run, which the fold lambdas capture by
+    // reference, it changes the register allocation of the whole kernel; likewise the four epilogues differ in which waves hold keys.)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float m2 = __shfl_xor(m_run, o), z2 = __shfl_xor(z_run, o);
@@ -594,7 +558,7 @@ __global__ __launch_bounds__(EM_THREADS, 2) void ea_logits_mfma_tri_kernel(EaArg
     float* lrow = logits + (size_t)bhq * a.Sp;
     float m_run = KVP_NEG_INF, z_run = 0.f;
 
-    const uint32_t ldsbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
+    const uint32_t ldsbase = KVP_LDS_ADDR(lds);
     const uint32_t dg = lane >> 4, di16 = lane & 15;
     // Round 6: a tile that lies inside the sequence is requested with ONE per-lane offset (row 4 wv + dg of a 16-row group, swizzled chunk:
     // the same for all eight groups, 16 j does not touch the row's low bits) on top of a SCALAR base that advances by 16 rows per request --
@@ -612,7 +576,7 @@ __global__ __launch_bounds__(EM_THREADS, 2) void ea_logits_mfma_tri_kernel(EaArg
                 const uint64_t sj = (uint64_t)(uintptr_t)(sb + (int64_t)(16 * j) * row_bytes);
                 const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)sj), hi = __builtin_amdgcn_readfirstlane((uint32_t)(sj >> 32));
                 const uint64_t sbase = ((uint64_t)hi << 32) | lo;
-                asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(la), "v"(goff), "s"(sbase) : "memory");
+                KVP_LDS_DMA16_SBASE(la, sbase, goff);
             }
             return;
         }
@@ -621,8 +585,7 @@ __global__ __launch_bounds__(EM_THREADS, 2) void ea_logits_mfma_tri_kernel(EaArg
             const uint32_t trow = 16 * j + 4 * wv + dg;
             const uint32_t r = min(row0 + trow, a.Sp - 1);
             const char* gp = kb + (int64_t)r * row_bytes + ((di16 ^ (trow & 15)) << 4);
-            const uint32_t la = __builtin_amdgcn_readfirstlane(ldsbase + buf_off + (16 * j + 4 * wv) * EM_ROWB);
-            asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(la), "v"(gp) : "memory");
+            lds_dma16(__builtin_amdgcn_readfirstlane(ldsbase + buf_off + (16 * j + 4 * wv) * EM_ROWB), gp);
         }
     };
     auto fold = [&](uint32_t tile, uint32_t rb) {
@@ -700,7 +663,7 @@ __global__ __launch_bounds__(EM_THREADS, 2) void ea_logits_mfma_tri_kernel(EaArg
 #pragma unroll
         for (int q = 0; q < 4; ++q) krBb[q] = make_uint2(0, 0);   // tile 0 has no predecessor: its deferred row-dot writes zeros nobody reads
         uint32_t rcur = 0, rprev = 2;
-        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this wave's part of tile 0 has landed
+        dma_wait<0>();   // vmcnt(0): this wave's part of tile 0 has landed
         __syncthreads();                      // (also publishes mus)
         acc_init(SA, acc0);
         acc_init(SB, acc1);
@@ -747,7 +710,7 @@ __global__ __launch_bounds__(EM_THREADS, 2) void ea_logits_mfma_tri_kernel(EaArg
             }
             EL_TRI_GROUP(2 * NB, 0, 26)
             __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): tile t + 1 has landed
+            dma_wait<0>();   // vmcnt(0): tile t + 1 has landed
             __syncthreads();
             unsigned char* tmp = bufc; bufc = bufn; bufn = tmp;
             if (t > 0) fold(t - 1, rprev);
@@ -785,20 +748,11 @@ __global__ __launch_bounds__(EM_THREADS, 2) void ea_logits_mfma_tri_kernel(EaArg
 // with one cross-lane read and owns its 32 logits (store + running softmax partial): no partial-sum buffers, one barrier per tile (the K ring).
 // K rows of 128 bytes sit two per LDS bank line, so their 16-byte slots rotate with bits 1 .. 3 of the row; rows of 192 bytes keep 256-byte LDS
 // rows and the lanes whose chunk does not exist request nothing (as snapkv_mfma.hip's KGeo).  Compiler-scheduled: these shapes are not the benchmark's.
-template <int DK> struct ElGeo {
+template <int DK> struct ElGeo : KTileGeo<DK, EM_THREADS> {   // (kvp_mfma.h: row bytes, rows per request, slot swizzle)
     static constexpr int D = DK * 16;
-    static constexpr int NS = DK / 2;                     // 32-row strips of U
-    static constexpr int ROWB = DK == 4 ? 128 : 256;      // bytes per key row IN LDS
-    static constexpr int NCH = DK * 2;                    // 16-byte chunks a key row has
-    static constexpr int CPR = ROWB / 16;
-    static constexpr int RPW = 1024 / ROWB;               // rows one wave's request moves
-    static constexpr int RPR = (EM_THREADS / 64) * RPW;   // rows one request of the workgroup moves
-    static constexpr int NREQ = EL_TILE / RPR;
-    static constexpr int TILEB = EL_TILE * ROWB;
     static constexpr int OCC = DK == 4 ? 3 : 2;           // workgroups per CU (registers: 6 / 12 hi + lo fragment pairs -- four per CU spilled five; LDS: 2 x 16 / 32 KiB)
-    static_assert(RPR % 16 == 0 && EL_TILE % RPR == 0, "the swizzle of a row depends on its index inside a request only");
-    static __device__ __forceinline__ uint32_t sw(uint32_t row) { return DK == 4 ? ((row >> 1) & 7u) : (row & 15u); }
 };
+static_assert(ElGeo<4>::TILE == EL_TILE, "tile size");
 template <int DT, int DK, int S_> struct ElSmallFrag { uint4 hi[DK - 2 * S_], lo[DK - 2 * S_]; };
 
 // BATCH > 0: a scheduling barrier after every BATCH fragments -- the compiler otherwise hoists ALL their loads to the top (16 values per fragment:
@@ -858,7 +812,7 @@ __global__ __launch_bounds__(EM_THREADS, ElGeo<DK>::OCC) void ea_logits_mfma_sma
     float* lrow = logits + (size_t)bhq * a.Sp;
     float m_run = KVP_NEG_INF, z_run = 0.f;   // lanes 0 .. 31 of every wave: the keys they own
 
-    const uint32_t ldsbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
+    const uint32_t ldsbase = KVP_LDS_ADDR(lds);
     const uint32_t rrow = Geo::RPW * wv + lane / Geo::CPR;                 // this lane's row inside a request
     const uint32_t rchunk = (lane % Geo::CPR) ^ Geo::sw(rrow);             // (a request's first row is a multiple of the swizzle period)
     auto request_tile = [&](uint32_t row0, uint32_t buf_off) {
@@ -867,11 +821,10 @@ __global__ __launch_bounds__(EM_THREADS, ElGeo<DK>::OCC) void ea_logits_mfma_sma
             const uint32_t r = min(row0 + Geo::RPR * j + rrow, a.Sp - 1);   // rows past the end: any valid row (never stored)
             const char* gp = kb + (int64_t)r * row_bytes + (rchunk << 4);
             const uint32_t la = __builtin_amdgcn_readfirstlane(ldsbase + buf_off + (Geo::RPR * j + Geo::RPW * wv) * Geo::ROWB);
-            if (Geo::NCH == Geo::CPR) {
-                asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(la), "v"(gp) : "memory");
-            } else {
-                asm volatile("s_mov_b32 m0, %0" ::"s"(la) : "memory");
-                if (rchunk < (uint32_t)Geo::NCH) asm volatile("global_load_lds_dwordx4 %0, off" ::"v"(gp) : "memory");
+            if (Geo::NCH == Geo::CPR) lds_dma16(la, gp);
+            else {
+                lds_dma_set_m0(la);
+                if (rchunk < (uint32_t)Geo::NCH) lds_dma16_at_m0(gp);
             }
         }
     };
@@ -919,7 +872,7 @@ __global__ __launch_bounds__(EM_THREADS, ElGeo<DK>::OCC) void ea_logits_mfma_sma
     };
     unsigned char* bufc = lds;
     unsigned char* bufn = lds + Geo::TILEB;
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this wave's part of tile 0 has landed
+    dma_wait<0>();   // vmcnt(0): this wave's part of tile 0 has landed
     __syncthreads();                      // (also publishes mus)
     for (uint32_t t = 0; t < ntiles; ++t) {
         const uint32_t key0 = kbeg + t * EL_TILE;
@@ -939,7 +892,7 @@ __global__ __launch_bounds__(EM_THREADS, ElGeo<DK>::OCC) void ea_logits_mfma_sma
             lrow[kk] = l2;
             softmax_merge(m_run, z_run, l2, 1.0f);
         }
-        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): tile t + 1 has landed (this wave's part; the barrier covers the others)
+        dma_wait<0>();   // vmcnt(0): tile t + 1 has landed (this wave's part; the barrier covers the others)
         __syncthreads();
         unsigned char* tmp = bufc; bufc = bufn; bufn = tmp;
     }
@@ -1004,7 +957,7 @@ __global__ __launch_bounds__(EB_THREADS, 1) void ea_logits_mfma_big_kernel(EaArg
 
     // LDS-DMA: request j (0 .. 15) of a tile moves rows 8 j + 2 wv + lane / 32; lane slot p = lane % 32 fetches chunk p ^ (row & 15) (bit 4 of the
     // chunk -- the 256-byte half -- stays): the rows of a request alternate between two swizzle phases (8 j is 0 or 8 mod 16)
-    const uint32_t ldsbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
+    const uint32_t ldsbase = KVP_LDS_ADDR(lds);
     const uint32_t rrow = 2 * wv + (lane >> 5);
     const uint32_t rch0 = ((lane & 31) ^ (rrow & 15)) << 4, rch1 = ((lane & 31) ^ ((rrow + 8) & 15)) << 4;
     auto request_tile = [&](uint32_t row0, uint32_t buf_off) {
@@ -1012,8 +965,7 @@ __global__ __launch_bounds__(EB_THREADS, 1) void ea_logits_mfma_big_kernel(EaArg
         for (int j = 0; j < 16; ++j) {
             const uint32_t r = min(row0 + 8 * j + rrow, a.Sp - 1);   // rows past the end: any valid row (never stored)
             const char* gp = kb + (int64_t)r * row_bytes + ((j & 1) ? rch1 : rch0);
-            const uint32_t la = __builtin_amdgcn_readfirstlane(ldsbase + buf_off + (8 * j + 2 * wv) * EB_ROWB);
-            asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(la), "v"(gp) : "memory");
+            lds_dma16(__builtin_amdgcn_readfirstlane(ldsbase + buf_off + (8 * j + 2 * wv) * EB_ROWB), gp);
         }
     };
     request_tile(kbeg, 0);
@@ -1068,7 +1020,7 @@ __global__ __launch_bounds__(EB_THREADS, 1) void ea_logits_mfma_big_kernel(EaArg
         };
         unsigned char* bufc = lds;
         unsigned char* bufn = lds + EB_TILEB;
-        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this wave's part of tile 0 has landed
+        dma_wait<0>();   // vmcnt(0): this wave's part of tile 0 has landed
         __syncthreads();                      // (also publishes mus)
         for (uint32_t t = 0; t < ntiles; ++t) {
             if (t + 1 < ntiles) request_tile(kbeg + (t + 1) * EL_TILE, (uint32_t)(bufn - lds));   // into the buffer tile t - 1 left at the last barrier
@@ -1109,7 +1061,7 @@ __global__ __launch_bounds__(EB_THREADS, 1) void ea_logits_mfma_big_kernel(EaArg
                 v += __shfl_xor(v, 32);   // the two lane halves hold the two halves of a strip's dims
                 if (kg == 0) red[t & 1][wv][row + u * 32] = v;
             }
-            __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): tile t + 1 has landed (this wave's part; the barrier covers the others)
+            dma_wait<0>();   // vmcnt(0): tile t + 1 has landed (this wave's part; the barrier covers the others)
             __syncthreads();
             unsigned char* tmp = bufc; bufc = bufn; bufn = tmp;
             fold(t);

@@ -34,8 +34,13 @@ template <> struct Elem<KVP_BF16> {
     static __device__ __forceinline__ float ld(const T* p) { return __uint_as_float(((uint32_t)*p) << 16); }
 };
 
-__device__ __forceinline__ float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf16_hi(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }
+// the two 16-bit halves of a dword as floats
+template <int DT> __device__ __forceinline__ float lo16(uint32_t w);
+template <int DT> __device__ __forceinline__ float hi16(uint32_t w);
+template <> __device__ __forceinline__ float lo16<KVP_BF16>(uint32_t w) { return __uint_as_float(w << 16); }
+template <> __device__ __forceinline__ float hi16<KVP_BF16>(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }
+template <> __device__ __forceinline__ float lo16<KVP_F16>(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFFu)); }
+template <> __device__ __forceinline__ float hi16<KVP_F16>(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)); }
 
 // unpack a 16-byte vector into floats (4 for f32, 8 for f16/bf16)
 template <int DT> __device__ __forceinline__ void unpack16(const uint4& v, float* f);
@@ -43,10 +48,13 @@ template <> __device__ __forceinline__ void unpack16<KVP_F32>(const uint4& v, fl
     f[0] = __uint_as_float(v.x); f[1] = __uint_as_float(v.y); f[2] = __uint_as_float(v.z); f[3] = __uint_as_float(v.w);
 }
 template <> __device__ __forceinline__ void unpack16<KVP_BF16>(const uint4& v, float* f) {
-    f[0] = bf16_lo(v.x); f[1] = bf16_hi(v.x); f[2] = bf16_lo(v.y); f[3] = bf16_hi(v.y);
-    f[4] = bf16_lo(v.z); f[5] = bf16_hi(v.z); f[6] = bf16_lo(v.w); f[7] = bf16_hi(v.w);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        f[2 * i] = lo16<KVP_BF16>(w[i]); f[2 * i + 1] = hi16<KVP_BF16>(w[i]);
+    }
 }
-template <> __device__ __forceinline__ void unpack16<KVP_F16>(const uint4& v, float* f) {
+template <> __device__ __forceinline__ void unpack16<KVP_F16>(const uint4& v, float* f) {   // (a packed conversion per dword: not lo16 / hi16's scalar ones)
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -54,6 +62,39 @@ template <> __device__ __forceinline__ void unpack16<KVP_F16>(const uint4& v, fl
         h2 p = __builtin_bit_cast(h2, w[i]);
         f[2 * i] = (float)p.x; f[2 * i + 1] = (float)p.y;
     }
+}
+// sum of the squares of the elements of a 16-byte vector (one fma chain, element order)
+template <int DT> __device__ __forceinline__ float sumsq16(const uint4& v) {
+    float f[Elem<DT>::PER16];
+    unpack16<DT>(v, f);
+    float a = 0.f;
+#pragma unroll
+    for (int i = 0; i < Elem<DT>::PER16; ++i) a = fmaf(f[i], f[i], a);
+    return a;
+}
+
+// ---- rounding to the model dtype (round to nearest even) ---------------------------------------------------------------------------
+// Two families.  round_dt / to_dt / st_dt / pack2 use the hardware conversions through inline asm.  NEVER apply them directly to an
+// MFMA accumulator: the asm reads the accumulator registers with no wait states after the MFMA that writes them (the compiler pads
+// hazards around its own instructions, not inside asm), which read partly written accumulators on hardware.  After an MFMA use the
+// asm-free round_acc / to_dt_acc.
+// bf16 by integer arithmetic: fin() receives the rounded pattern in the upper 16 bits (the lower ones are whatever the carry left; NaN
+// stays a quiet NaN) and masks or shifts it -- inside each branch, which is the shape both users were compiled from
+template <typename F> __device__ __forceinline__ auto bf16_rne(float x, F fin) {
+    const uint32_t u = __float_as_uint(x);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return fin(u | 0x00400000u);
+    return fin(u + 0x7FFFu + ((u >> 16) & 1u));
+}
+template <int DT> __device__ __forceinline__ float round_acc(float x);
+template <> __device__ __forceinline__ float round_acc<KVP_F16>(float x) { return (float)(_Float16)x; }
+template <> __device__ __forceinline__ float round_acc<KVP_BF16>(float x) {
+    return bf16_rne(x, [](uint32_t r) { return __uint_as_float(r & 0xFFFF0000u); });
+}
+template <int DT> __device__ __forceinline__ typename Elem<DT>::T to_dt_acc(float x);
+template <> __device__ __forceinline__ float to_dt_acc<KVP_F32>(float x) { return x; }
+template <> __device__ __forceinline__ _Float16 to_dt_acc<KVP_F16>(float x) { return (_Float16)x; }
+template <> __device__ __forceinline__ uint16_t to_dt_acc<KVP_BF16>(float x) {
+    return bf16_rne(x, [](uint32_t r) { return (uint16_t)(r >> 16); });
 }
 
 // value rounded to the storage dtype and back (torch's eager ops round after every mul / add in the model dtype)
@@ -74,11 +115,34 @@ template <> __device__ __forceinline__ float round_dt<KVP_BF16>(float x) {  // r
     asm("v_cvt_pk_bf16_f32 %0, %1, %1" : "=v"(r) : "v"(x));
     return __uint_as_float(r << 16);
 #else   // any other target of a stray --offload-arch: the integer round-to-nearest-even (NaN stays a quiet NaN)
-    const uint32_t u = __float_as_uint(x);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return __uint_as_float((u | 0x00400000u) & 0xFFFF0000u);
-    return __uint_as_float((u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u);
+    return round_acc<KVP_BF16>(x);
 #endif
 }
+// float -> a stored element of the model dtype (torch's .to(dtype))
+template <int DT> __device__ __forceinline__ typename Elem<DT>::T to_dt(float x);
+template <> __device__ __forceinline__ float to_dt<KVP_F32>(float x) { return x; }
+template <> __device__ __forceinline__ _Float16 to_dt<KVP_F16>(float x) { return (_Float16)x; }
+template <> __device__ __forceinline__ uint16_t to_dt<KVP_BF16>(float x) { return (uint16_t)(__float_as_uint(round_dt<KVP_BF16>(x)) >> 16); }
+template <int DT> __device__ __forceinline__ void st_dt(typename Elem<DT>::T* p, float x) { *p = to_dt<DT>(x); }
+// two floats -> one dword of 16-bit values, low half = lo: one conversion instruction
+template <int DT> __device__ __forceinline__ uint32_t pack2(float lo, float hi);
+template <> __device__ __forceinline__ uint32_t pack2<KVP_BF16>(float lo, float hi) {
+    uint32_t r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+    return r;
+}
+template <> __device__ __forceinline__ uint32_t pack2<KVP_F16>(float lo, float hi) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    h2 p = {(_Float16)lo, (_Float16)hi};
+    return __builtin_bit_cast(uint32_t, p);
+}
+// the same dword from two round_dt conversions: the form the RoPE kernels were built and measured with (pack2 computes the same bits
+// with fewer instructions, but it is another kernel: switching needs a timing of its own)
+template <int DT> __device__ __forceinline__ uint32_t join2(float lo, float hi);
+template <> __device__ __forceinline__ uint32_t join2<KVP_BF16>(float lo, float hi) {
+    return (__float_as_uint(round_dt<KVP_BF16>(lo)) >> 16) | (__float_as_uint(round_dt<KVP_BF16>(hi)) & 0xFFFF0000u);
+}
+template <> __device__ __forceinline__ uint32_t join2<KVP_F16>(float lo, float hi) { return pack2<KVP_F16>(lo, hi); }
 // one RoPE output element with torch's rounding: round(round(a * ca) + round(b * sb)); __fmul_rn / __fadd_rn keep the
 // ops separately rounded as in torch's eager mul, mul, add (never contracted to an fma)
 template <int DT> __device__ __forceinline__ float rope_elem(float a, float ca, float b, float sb) {
@@ -104,6 +168,7 @@ template <bool NT> __device__ __forceinline__ void st16(void* p, const uint4& v)
 }
 
 // ---- wave / block reductions -----------------------------------------------------------------
+// butterflies over the wave's 64 lanes: every lane ends with the result
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -114,10 +179,28 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
+    return v;
+}
 
-// float <-> order-preserving uint32 (larger float <=> larger key); -0.0 is canonicalised to +0.0
+// a value that every lane holds identically, moved to scalar registers: branches on it are scalar branches (no saved exec masks), and
+// values handed to an asm block through "s" constraints must sit in SGPRs
+__device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+__device__ __forceinline__ float uni(float x) { return __uint_as_float(uni(__float_as_uint(x))); }
+template <typename T> __device__ __forceinline__ T* uni(T* p) {
+    const uint64_t v = (uint64_t)(uintptr_t)p;
+    return (T*)(uintptr_t)(((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v));
+}
+
+// float <-> order-preserving uint32 (larger float <=> larger key; atomicMax / radix select over floats of any sign); -0.0 is canonicalised to +0.0
 __device__ __forceinline__ uint32_t float_to_key(float f) {
     uint32_t u = __float_as_uint(f);
     if (u == 0x80000000u) u = 0u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_to_float(uint32_t k) {
+    const uint32_t u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
+    return __uint_as_float(u);
 }

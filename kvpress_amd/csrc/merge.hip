@@ -13,13 +13,9 @@
 // bit-identical from run to run.  Workspace: 32 bytes per (b, h, token) plus O(B*H*S/1024) (kvp_merge_workspace_bytes).
 #include <math.h>
 
-#include "kvp_common.h"
+#include "kvp_mfma.h"
 
 namespace {
-
-typedef __bf16 mrg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 mrg_f16x8 __attribute__((ext_vector_type(8)));
-typedef float mrg_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int MT = 256;          // threads of the element-wise kernels
 constexpr int TILE = 1024;       // positions per compaction tile
@@ -29,24 +25,6 @@ constexpr int AM_KT = 64;        // kept rows staged per LDS buffer
 constexpr int GN_EV = 32;        // generic argmax: evicted rows per workgroup
 constexpr int GN_KT = 16;        // generic argmax: kept rows per LDS tile
 constexpr float EPS = 1e-6f;     // merging_press.py:14
-
-template <int DT> __device__ __forceinline__ mrg_f32x16 mfma32(const uint4& a, const uint4& b, const mrg_f32x16& c);
-template <> __device__ __forceinline__ mrg_f32x16 mfma32<KVP_BF16>(const uint4& a, const uint4& b, const mrg_f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(mrg_bf16x8, a), __builtin_bit_cast(mrg_bf16x8, b), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ mrg_f32x16 mfma32<KVP_F16>(const uint4& a, const uint4& b, const mrg_f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(mrg_f16x8, a), __builtin_bit_cast(mrg_f16x8, b), c, 0, 0, 0);
-}
-
-// float -> model dtype with torch's .to(dtype) rounding (RNE), returned as the storage bits
-template <int DT> __device__ __forceinline__ typename Elem<DT>::T to_dt(float x);
-template <> __device__ __forceinline__ float to_dt<KVP_F32>(float x) { return x; }
-template <> __device__ __forceinline__ _Float16 to_dt<KVP_F16>(float x) { return (_Float16)x; }
-template <> __device__ __forceinline__ uint16_t to_dt<KVP_BF16>(float x) {
-    const uint32_t u = __float_as_uint(x);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u | 0x00400000u) >> 16);
-    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
 
 // (value, index) of the better candidate: larger value, ties to the lower index; NaN never wins
 __device__ __forceinline__ void better(float& bv, int& bi, float v, int i) {
@@ -100,7 +78,7 @@ __global__ __launch_bounds__(MT) void mrg_tile_count_kernel(const int32_t* __res
         if (s < S && cnt[r * (S + 1) + s] == 0) ++c;
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);   // (written out: through a wave_sum call the scheduler moves the wave-index shift below)
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -267,7 +245,7 @@ __global__ __launch_bounds__(AM_WAVES * 64) void mrg_argmax_mfma_kernel(
         for (int sub = 0; sub < AM_KT / 32; ++sub) {
             if (t0 + sub * 32 >= k1) break;
             const int row = sub * 32 + r32;
-            mrg_f32x16 acc[G::NB];
+            f32x16 acc[G::NB];
 #pragma unroll
             for (int nb = 0; nb < G::NB; ++nb)
 #pragma unroll
@@ -276,7 +254,7 @@ __global__ __launch_bounds__(AM_WAVES * 64) void mrg_argmax_mfma_kernel(
             for (int s = 0; s < G::KS; ++s) {
                 const uint4 a = *reinterpret_cast<const uint4*>(&ks[row * D + G::swz(row, 2 * s + h) * 8]);
 #pragma unroll
-                for (int nb = 0; nb < G::NB; ++nb) acc[nb] = mfma32<DT>(a, bq[nb][s], acc[nb]);
+                for (int nb = 0; nb < G::NB; ++nb) acc[nb] = mma32<DT>(a, bq[nb][s], acc[nb]);
             }
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
@@ -421,9 +399,6 @@ __device__ uint32_t radix_select(const float* __restrict__ x, int64_t n, float t
     }
     return prefix;
 }
-__device__ __forceinline__ float key_to_float(uint32_t key) {
-    return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-}
 
 // torch.quantile(q, dim=-1) of max_sim.masked_fill(~ok, -inf) per row (:146-150): rank = q * (n - 1) in float32, the floor and ceil
 // order statistics, lerp as ATen evaluates it -- NaN when the lower statistic is -inf and the weight < 0.5 (or both are -inf)
@@ -546,7 +521,7 @@ __global__ __launch_bounds__(MT) void mrg_merge_kernel(const typename Elem<DT>::
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int d = lane + 64 * q;
-        if (d < D) orow[d] = to_dt<DT>(__fadd_rn(Elem<DT>::ld(orow + d), acc[q]) / den);
+        if (d < D) orow[d] = to_dt_acc<DT>(__fadd_rn(Elem<DT>::ld(orow + d), acc[q]) / den);   // (integer rounding: the form this kernel was compiled with, no MFMA involved)
     }
 }
 

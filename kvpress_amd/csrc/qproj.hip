@@ -29,13 +29,9 @@
 // isolation).  Round 5 built the split over the hidden dimension properly (64 columns x K/4 per workgroup: 64 MiB of traffic, float32
 // partials + a reduce / RoPE kernel; tools/lab_patches/qproj_splitk.diff): same step time on the same box (0.2705 vs 0.2695 ms,
 // profiles/r05_ab_qproj.txt) and +3 us on short caches -- the fixed cost of 256 short-lived streaming workgroups, not the L2 -> CU bytes, is what is left.
-#include "kvp_common.h"
+#include "kvp_mfma.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int QP_THREADS = 512;
 constexpr int QP_WAVES = QP_THREADS / 64;  // one 32-element k-step of every K tile per wave
@@ -47,18 +43,6 @@ constexpr int QP_TILEB = (QP_COLS + QP_ROWS) * QP_ROWB;    // 8 KiB of weights +
 constexpr int QP_REQ = QP_TILEB / 16 / QP_THREADS;         // LDS-DMA requests per thread and tile (5)
 constexpr int QP_NBUF = 3;
 static_assert(QP_TILEB % (16 * QP_THREADS) == 0, "whole requests");
-
-template <int DT> __device__ __forceinline__ f32x4 mma16(const uint4& a, const uint4& b, f32x4 c);
-template <> __device__ __forceinline__ f32x4 mma16<KVP_BF16>(const uint4& a, const uint4& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ f32x4 mma16<KVP_F16>(const uint4& a, const uint4& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-template <int DT> __device__ __forceinline__ void st_dt(typename Elem<DT>::T* p, float x);
-template <> __device__ __forceinline__ void st_dt<KVP_F16>(_Float16* p, float x) { *p = (_Float16)x; }
-template <> __device__ __forceinline__ void st_dt<KVP_BF16>(uint16_t* p, float x) { *p = (uint16_t)(__float_as_uint(round_dt<KVP_BF16>(x)) >> 16); }
 
 struct QprojArgs {
     const char* x;      // hidden window [B, 64, K]
@@ -110,14 +94,12 @@ __global__ __launch_bounds__(QP_THREADS) void qproj_rope_kernel(QprojArgs a) {
 #pragma unroll
         for (int i = 0; i < QP_REQ; ++i) {
             const char* g = gsrc[i] + (int64_t)tt * QP_ROWB;
-            const uint32_t la = __builtin_amdgcn_readfirstlane(
-                (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)(lds + buf * QP_TILEB + (i * QP_THREADS + wv * 64) * 16));
-            asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(la), "v"(g) : "memory");
+            lds_dma16(__builtin_amdgcn_readfirstlane(KVP_LDS_ADDR(lds + buf * QP_TILEB + (i * QP_THREADS + wv * 64) * 16)), g);
         }
     };
 #pragma unroll
     for (int p = 0; p < QP_NBUF - 1; ++p) request_tile(p, p);
-    __builtin_amdgcn_s_waitcnt(0x0F70 | ((QP_NBUF - 2) * QP_REQ));  // tile 0 landed (the newer tiles may still be in flight)
+    dma_wait<(QP_NBUF - 2) * QP_REQ>();  // tile 0 landed (the newer tiles may still be in flight)
     __syncthreads();
 
     f32x4 acc[4];
@@ -135,11 +117,11 @@ __global__ __launch_bounds__(QP_THREADS) void qproj_rope_kernel(QprojArgs a) {
             afrag[m] = *reinterpret_cast<const uint4*>(buf + (QP_COLS + 16 * m + l16) * QP_ROWB + sl);
 #pragma unroll
         for (int m = 0; m < 4; ++m) acc[m] = mma16<DT>(afrag[m], bfrag, acc[m]);  // C[row 16 m + 4 kq + r][col l16]
-        __builtin_amdgcn_s_waitcnt(0x0070 | ((QP_NBUF - 2) * QP_REQ));  // lgkmcnt(0) + tile t+1 landed
+        dma_wait<(QP_NBUF - 2) * QP_REQ, true>();  // every LDS read done + tile t+1 landed
         __syncthreads();
         bc = bc + 1 == QP_NBUF ? 0 : bc + 1;
     }
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // drain the DMA before the buffers are reused for the partial sums
+    dma_wait<0>();  // drain the DMA before the buffers are reused for the partial sums
 
     float (*part)[QP_ROWS][QP_COLS + 1] = reinterpret_cast<float (*)[QP_ROWS][QP_COLS + 1]>(lds);  // [k-step][row][col]
     __syncthreads();

@@ -8,11 +8,6 @@
 
 namespace {
 
-template <int DT> __device__ __forceinline__ void st_elem(typename Elem<DT>::T* p, float x);
-template <> __device__ __forceinline__ void st_elem<KVP_F32>(float* p, float x) { *p = x; }
-template <> __device__ __forceinline__ void st_elem<KVP_F16>(_Float16* p, float x) { *p = (_Float16)x; }
-template <> __device__ __forceinline__ void st_elem<KVP_BF16>(uint16_t* p, float x) { *p = (uint16_t)(__float_as_uint(round_dt<KVP_BF16>(x)) >> 16); }
-
 // cos / sin of a float32 angle (torch: `freqs.cos()`, `.sin()` of the float32 product delta * inv_freq).  The angles reach ~1e5 rad,
 // where cosf and sinf each run their slow argument reduction (140 of the kernel's 150 us at 8 x 65536 rows).  Instead: ONE reduction
 // in double -- k = rint(angle * 2/pi), r = (angle * 2/pi - k) * pi/2 in [-pi/4, pi/4], exact to ~1e-16 of a quarter turn -- then the
@@ -54,22 +49,13 @@ __global__ __launch_bounds__(256) void rerotate_kernel(typename Elem<DT>::T* __r
         const float c = round_dt<DT>(cv), s = round_dt<DT>(sv);  // same angle for d and d + half
         typename Elem<DT>::T* row = kb + (size_t)j * D;
         const float k0 = Elem<DT>::ld(row + d), k1 = Elem<DT>::ld(row + d + half);
-        st_elem<DT>(row + d, rope_elem<DT>(k0, c, -k1, s));
-        st_elem<DT>(row + d + half, rope_elem<DT>(k1, c, k0, s));
+        st_dt<DT>(row + d, rope_elem<DT>(k0, c, -k1, s));
+        st_dt<DT>(row + d + half, rope_elem<DT>(k1, c, k0, s));
     }
 }
 
 // 2-byte dtypes, D % 16 == 0, 16-byte aligned rows: a thread owns 8 consecutive dims d0 .. d0+7 of the first half and the matching 8 of
 // the second half: two 16-byte loads, 8 angles, two 16-byte stores (the scalar kernel above moves 2 bytes per lane and instruction).
-template <int DT> __device__ __forceinline__ uint32_t pack2(float lo, float hi);
-template <> __device__ __forceinline__ uint32_t pack2<KVP_BF16>(float lo, float hi) {
-    return (__float_as_uint(round_dt<KVP_BF16>(lo)) >> 16) | (__float_as_uint(round_dt<KVP_BF16>(hi)) & 0xFFFF0000u);
-}
-template <> __device__ __forceinline__ uint32_t pack2<KVP_F16>(float lo, float hi) {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    h2 v = {(_Float16)lo, (_Float16)hi};
-    return __builtin_bit_cast(uint32_t, v);
-}
 // dims d0 .. d0+7 of the first half (a) and of the second half (b) of one row, rotated by delta * inv_freq[d0 .. d0+7]
 template <int DT>
 __device__ __forceinline__ void rotate8(const uint4& a, const uint4& b, float delta, const float* __restrict__ invf, uint4& out0, uint4& out1) {
@@ -87,8 +73,8 @@ __device__ __forceinline__ void rotate8(const uint4& a, const uint4& b, float de
         o0[e] = rope_elem<DT>(k0[e], c, -k1[e], s);
         o1[e] = rope_elem<DT>(k1[e], c, k0[e], s);
     }
-    out0 = make_uint4(pack2<DT>(o0[0], o0[1]), pack2<DT>(o0[2], o0[3]), pack2<DT>(o0[4], o0[5]), pack2<DT>(o0[6], o0[7]));
-    out1 = make_uint4(pack2<DT>(o1[0], o1[1]), pack2<DT>(o1[2], o1[3]), pack2<DT>(o1[4], o1[5]), pack2<DT>(o1[6], o1[7]));
+    out0 = make_uint4(join2<DT>(o0[0], o0[1]), join2<DT>(o0[2], o0[3]), join2<DT>(o0[4], o0[5]), join2<DT>(o0[6], o0[7]));
+    out1 = make_uint4(join2<DT>(o1[0], o1[1]), join2<DT>(o1[2], o1[3]), join2<DT>(o1[4], o1[5]), join2<DT>(o1[6], o1[7]));
 }
 
 template <int DT>

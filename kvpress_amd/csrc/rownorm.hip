@@ -13,16 +13,6 @@
 
 namespace {
 
-template <int DT>
-__device__ __forceinline__ float sumsq16(const uint4& v) {
-    float f[Elem<DT>::PER16];
-    unpack16<DT>(v, f);
-    float a = 0.f;
-#pragma unroll
-    for (int i = 0; i < Elem<DT>::PER16; ++i) a = fmaf(f[i], f[i], a);
-    return a;
-}
-
 constexpr int RN_THREADS = 256;
 constexpr int RN_UNROLL = 4;
 

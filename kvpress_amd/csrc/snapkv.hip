@@ -153,11 +153,6 @@ __global__ __launch_bounds__(SK_THREADS) void snapkv_colsum_from_attn(const type
 }
 
 // ---- RoPE of the window queries: q*cos + rotate_half(q)*sin, with torch's per-op rounding --------
-template <int DT> __device__ __forceinline__ void st_dt(typename Elem<DT>::T* p, float x);
-template <> __device__ __forceinline__ void st_dt<KVP_F32>(float* p, float x) { *p = x; }
-template <> __device__ __forceinline__ void st_dt<KVP_F16>(_Float16* p, float x) { *p = (_Float16)x; }
-template <> __device__ __forceinline__ void st_dt<KVP_BF16>(uint16_t* p, float x) { *p = (uint16_t)(__float_as_uint(round_dt<KVP_BF16>(x)) >> 16); }
-
 // one thread per (row, d < D/2): out[d] = q[d]*cos[d] - q[d+h]*sin[d];  out[d+h] = q[d+h]*cos[d+h] + q[d]*sin[d+h]
 template <int DT>
 __global__ __launch_bounds__(SK_THREADS) void snapkv_rope_kernel(const typename Elem<DT>::T* __restrict__ q, int64_t q_sb,
@@ -187,15 +182,6 @@ __global__ __launch_bounds__(SK_THREADS) void snapkv_rope_kernel(const typename 
 // 2-byte dtypes, D % 16 == 0, 16-byte aligned rows: a thread owns 8 consecutive dims of the first half and the matching 8 of the second
 // half (six 16-byte loads, two 16-byte stores; the same rope_elem arithmetic: bit-identical).  The scalar kernel above moves 2 bytes per
 // lane and instruction and divides three times per element: 81 us for the 33.5 M elements of a 128-chunk ChunkPress window batch.
-template <int DT> __device__ __forceinline__ uint32_t rope_pack2(float lo, float hi);
-template <> __device__ __forceinline__ uint32_t rope_pack2<KVP_BF16>(float lo, float hi) {
-    return (__float_as_uint(round_dt<KVP_BF16>(lo)) >> 16) | (__float_as_uint(round_dt<KVP_BF16>(hi)) & 0xFFFF0000u);
-}
-template <> __device__ __forceinline__ uint32_t rope_pack2<KVP_F16>(float lo, float hi) {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    h2 v = {(_Float16)lo, (_Float16)hi};
-    return __builtin_bit_cast(uint32_t, v);
-}
 template <int DT>
 __global__ __launch_bounds__(SK_THREADS) void snapkv_rope_vec_kernel(const typename Elem<DT>::T* __restrict__ q, int64_t q_sb, int64_t q_sh, int64_t q_sw,
                                                                      const typename Elem<DT>::T* __restrict__ cosp,
@@ -223,8 +209,8 @@ __global__ __launch_bounds__(SK_THREADS) void snapkv_rope_vec_kernel(const typen
             hi[e] = rope_elem<DT>(q1[e], c1[e], q0[e], s1[e]);
         }
         typename Elem<DT>::T* o = out + (size_t)row * D;
-        *reinterpret_cast<uint4*>(o + d0) = make_uint4(rope_pack2<DT>(lo[0], lo[1]), rope_pack2<DT>(lo[2], lo[3]), rope_pack2<DT>(lo[4], lo[5]), rope_pack2<DT>(lo[6], lo[7]));
-        *reinterpret_cast<uint4*>(o + d0 + half) = make_uint4(rope_pack2<DT>(hi[0], hi[1]), rope_pack2<DT>(hi[2], hi[3]), rope_pack2<DT>(hi[4], hi[5]), rope_pack2<DT>(hi[6], hi[7]));
+        *reinterpret_cast<uint4*>(o + d0) = make_uint4(join2<DT>(lo[0], lo[1]), join2<DT>(lo[2], lo[3]), join2<DT>(lo[4], lo[5]), join2<DT>(lo[6], lo[7]));
+        *reinterpret_cast<uint4*>(o + d0 + half) = make_uint4(join2<DT>(hi[0], hi[1]), join2<DT>(hi[2], hi[3]), join2<DT>(hi[4], hi[5]), join2<DT>(hi[6], hi[7]));
     }
 }
 

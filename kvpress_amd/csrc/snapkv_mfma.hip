@@ -30,7 +30,7 @@
 // accumulators and fragment registers).  On a gfx950 SIMD MFMAs and VALU instructions do not overlap
 // (tools/ubench_valu.hip, ubench_overlap.hip), so the per-sub-tile cost is ~272 cycles of MFMA + ~290 of VALU.
 // The causal mask exists only in pass 1 and only in the last tiles of a row.
-#include "kvp_common.h"
+#include "kvp_mfma.h"
 #include "softmax_stats.h"
 #include "snapkv_internal.h"
 #include "snapkv_asm.inc"
@@ -38,10 +38,6 @@
 #include <vector>
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int MF_THREADS = 512;      // 8 waves
 constexpr int MF_WAVES = MF_THREADS / 64;
@@ -55,31 +51,13 @@ static_assert(MF_TILEB / 16 / MF_THREADS == MF_SUBS, "one DMA request per thread
 // Geometry of a K tile for a head of DK k-steps of 16 elements (round 6: D = 128 -> DK = 8, D = 64 -> DK = 4; D = 96 -> DK = 6 keeps the
 // 256-byte LDS rows of DK = 8 and simply never requests the four chunks a 192-byte key row does not have; D = 256 -> DK = 16: 64 KiB
 // tiles, so a ring of TWO buffers (one tile of prefetch) and single-buffered fragment registers; 2-byte elements).
-template <int DK> struct KGeo {
-    static constexpr int ROWB = DK == 6 ? 256 : DK * 32;   // bytes per key row IN LDS
-    static constexpr int NCH = DK * 2;              // 16-byte chunks a key row really has
-    static constexpr int CPR = ROWB / 16;           // 16-byte slots per LDS row
-    static constexpr int RPW = 1024 / ROWB;         // rows one wave's request moves (64 lanes x 16 bytes)
-    static constexpr int RPR = (MF_THREADS / 64) * RPW;   // rows one request of the workgroup moves
-    static constexpr int NREQ = MF_TILE / RPR;      // requests per thread and tile
-    static constexpr int TILEB = MF_TILE * ROWB;
+template <int DK> struct KGeo : KTileGeo<DK, MF_THREADS> {   // (kvp_mfma.h: row bytes, rows per request, slot swizzle)
     static constexpr int NBUF = DK <= 8 ? 3 : 2;    // LDS ring: NBUF - 1 tiles of prefetch (three 64 KiB tiles would not fit the CU's 160 KiB)
     static constexpr int NKF = DK <= 8 ? 2 : 1;     // fragment register sets: the next sub-tile's reads overlap this one's chain where they fit
-    static_assert(RPR % 16 == 0 && MF_TILE % RPR == 0, "the swizzle of a row (period: 16 rows) depends on its index inside a request only");
-    // XOR swizzle of a tile row's 16-byte slots: 16 consecutive rows of a fragment read must hit 16 distinct slots of the 256-byte
-    // bank line -- rows of 256 bytes: the row's low four bits; rows of 128 bytes (two per bank line): bits 1 .. 3
-    static __device__ __forceinline__ uint32_t sw(uint32_t row) { return DK == 4 ? ((row >> 1) & 7u) : (row & 15u); }
     static __device__ __forceinline__ int ring_next(int b) { return b + 1 == NBUF ? 0 : b + 1; }
     static __device__ __forceinline__ int ring_prev(int b) { return b == 0 ? NBUF - 1 : b - 1; }
 };
-
-template <int DT> __device__ __forceinline__ f32x16 mma32(const uint4& a, const uint4& b, f32x16 c);
-template <> __device__ __forceinline__ f32x16 mma32<KVP_BF16>(const uint4& a, const uint4& b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ f32x16 mma32<KVP_F16>(const uint4& a, const uint4& b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
+static_assert(KGeo<8>::TILE == MF_TILE, "tile size");
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
@@ -110,15 +88,9 @@ struct KStreamT {
     __device__ __forceinline__ void request(unsigned char* buf, uint32_t key0, int i) const {
         const uint32_t kk = min(key0 + i * Geo::RPR + lrow, S - 1);
         const char* g = kb + (int64_t)kk * k_ssb + choff;
-        const uint32_t la = __builtin_amdgcn_readfirstlane(
-            (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)(buf + (i * Geo::RPR + ldsrow) * Geo::ROWB));
-        // M0 is a reserved register that hipcc never keeps values in (nothing else in these kernels uses it)
-        if (Geo::NCH == Geo::CPR) {
-            asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(la), "v"(g) : "memory");
-        } else {
-            asm volatile("s_mov_b32 m0, %0" ::"s"(la) : "memory");   // (outside the divergent region: M0 is per wave)
-            if (has_chunk) asm volatile("global_load_lds_dwordx4 %0, off" ::"v"(g) : "memory");
-        }
+        const uint32_t la = __builtin_amdgcn_readfirstlane(KVP_LDS_ADDR(buf + (i * Geo::RPR + ldsrow) * Geo::ROWB));
+        if (Geo::NCH == Geo::CPR) lds_dma16(la, g);
+        else lds_dma16_if(has_chunk, la, g);
     }
     __device__ __forceinline__ void request_tile(unsigned char* buf, uint32_t key0) const {
 #pragma unroll
@@ -131,13 +103,9 @@ struct KStreamT {
     }
 };
 typedef KStreamT<8> KStream;
-// s_waitcnt through the builtin (simm16: vmcnt[3:0] | expcnt 7 << 4 | lgkmcnt 15 << 8): unlike an asm string, hipcc's own
-// wait-count bookkeeping sees it, so it stops re-waiting for the Q-fragment loads inside the tile loop.
-// only the newest tile's MF_SUBS requests of this wave may still be in flight
-__device__ __forceinline__ void wait_tile_landed() { __builtin_amdgcn_s_waitcnt(0x0F70 | MF_SUBS); }
-// (only the requests of tiles newer than t + 1 may still be in flight: (NBUF - 2) tiles' worth)
-template <int DK> __device__ __forceinline__ void wait_tile_landed_t() { __builtin_amdgcn_s_waitcnt(0x0F70 | ((KGeo<DK>::NBUF - 2) * KGeo<DK>::NREQ)); }
-__device__ __forceinline__ void wait_all_landed() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+// the wave's outstanding requests (dma_wait, kvp_mfma.h): only those of tiles newer than t + 1 may still be in flight, (NBUF - 2) tiles' worth
+template <int DK> __device__ __forceinline__ void wait_tile_landed_t() { dma_wait<(KGeo<DK>::NBUF - 2) * KGeo<DK>::NREQ>(); }
+__device__ __forceinline__ void wait_all_landed() { dma_wait<0>(); }
 
 // fragment of the 32-key sub-tile `sub` for k-step ks: lane (n = lane & 31, kg = lane >> 5)
 template <int DK>
@@ -176,8 +144,6 @@ struct TileWalk {
     }
     __device__ __forceinline__ uint32_t key0(uint32_t t) const { return min(kbeg + t * tstride, klast); }
 };
-__device__ __forceinline__ int ring_next(int b) { return b + 1 == MF_NBUF ? 0 : b + 1; }
-__device__ __forceinline__ int ring_prev(int b) { return b == 0 ? MF_NBUF - 1 : b - 1; }
 
 // ---- windows of any size (SnapArgs: Wp, rblk) ------------------------------------------------------------------------------------
 // The kernels work on ONE block of 64 padded window rows per launch.  Row r (0 .. 63) of block a.rblk is padded row p = 64 rblk + r:
@@ -348,22 +314,13 @@ __global__ __launch_bounds__(MF_THREADS, 2) void snapkv_p1_mfma(SnapArgs a, uint
 
     if (active) {
         float mm = m == KVP_NEG_INF ? KVP_NEG_INF : m * c, zz = z;
-        const float m2 = __shfl_xor(mm, 32), z2 = __shfl_xor(zz, 32);
-        softmax_merge(mm, zz, m2, z2);
+        wave_softmax_merge<32, 32>(mm, zz);
         if (kg == 0) {
             const size_t o = ((size_t)(b * a.Hq + hq) * a.Wp + mf_prow(a, w)) * nchunk + chunk;
             part_m[o] = mm;
             part_z[o] = zz;
         }
     }
-}
-
-// values handed to an asm block through "s" constraints must sit in SGPRs: make their uniformity explicit
-__device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ float uni(float x) { return __uint_as_float(uni(__float_as_uint(x))); }
-template <typename T> __device__ __forceinline__ T* uni(T* p) {
-    const uint64_t v = (uint64_t)(uintptr_t)p;
-    return (T*)(uintptr_t)(((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v));
 }
 
 // =================================================================================================
@@ -412,7 +369,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void snapkv_p1_asm(SnapArgs a, uint3
     float m = KVP_NEG_INF, z = 0.f;
     const float c = a.c;
     if (nasm) {
-        const uint32_t ldsbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
+        const uint32_t ldsbase = KVP_LDS_ADDR(lds);
         uint32_t la[8], vo[4];
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) la[ks] = ldsbase + n * MF_ROWB + (((ks * 2 + kg) ^ (n & 15)) << 4);
@@ -485,7 +442,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void snapkv_p1_asm(SnapArgs a, uint3
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_waitcnt(0x0F70 | (MF_SUBS * (NB - 2)));   // only the newer tiles' requests may still be in flight
+            dma_wait<MF_SUBS * (NB - 2)>();   // only the newer tiles' requests may still be in flight
             __syncthreads();
             bc = (bc + 1) % NB;
         }
@@ -493,8 +450,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void snapkv_p1_asm(SnapArgs a, uint3
     wait_all_landed();
 
     float mm = m == KVP_NEG_INF ? KVP_NEG_INF : m * c, zz = z;
-    const float m2 = __shfl_xor(mm, 32), z2 = __shfl_xor(zz, 32);
-    softmax_merge(mm, zz, m2, z2);
+    wave_softmax_merge<32, 32>(mm, zz);
     if (kg == 0) {
         const size_t o = ((size_t)(b * a.Hq + hq) * a.Wp + mf_prow(a, row0 + n)) * nchunk + chunk;
         part_m[o] = mm;
@@ -724,9 +680,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void snapkv_p2_asm(SnapArgs a, uint3
         const uint32_t nch = gridDim.x, total_tiles = (Sm + MF_TILE - 1) / MF_TILE;
         const uint32_t* tp = ticks + ((size_t)b * gridDim.y + blockIdx.y) * nch;
         const uint32_t tk = lane < nch ? max(tp[lane], 1u) : 0xFFFFFFFFu;
-        uint32_t tmin = tk;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) tmin = min(tmin, (uint32_t)__shfl_xor((int)tmin, o));
+        const uint32_t tmin = wave_min(tk);
         const float speed = lane < nch ? 1.0f / (float)min(tk, 2u * tmin) : 0.f;
         float incl = speed;
 #pragma unroll
@@ -756,8 +710,8 @@ __global__ __launch_bounds__(MF_THREADS, 2) void snapkv_p2_asm(SnapArgs a, uint3
     const uint32_t nasm = last_full ? nfast : min(nfast, tw.ntiles >= 3 ? tw.ntiles - 3 : 0u);
 
     if (nasm) {
-        const uint32_t ldsbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
-        const uint32_t redbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)red3;
+        const uint32_t ldsbase = KVP_LDS_ADDR(lds);
+        const uint32_t redbase = KVP_LDS_ADDR(red3);
         uint32_t la[8], vo[4];
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) la[ks] = ldsbase + n * MF_ROWB + (((ks * 2 + kg) ^ (n & 15)) << 4);
@@ -803,7 +757,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void snapkv_p2_asm(SnapArgs a, uint3
         int bc = nasm % 3;
         for (uint32_t t = nasm; t < tw.ntiles; ++t) {
             const unsigned char* buf = lds + bc * MF_TILEB;
-            unsigned char* bufr = lds + ring_prev(bc) * MF_TILEB;
+            unsigned char* bufr = lds + KGeo<8>::ring_prev(bc) * MF_TILEB;
             const uint32_t key0 = tw.key0(t), keyr = tw.key0(t + 2);
             const int par = t & 1;
             for (int sub = 0; sub < MF_SUBS; ++sub) {
@@ -827,7 +781,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void snapkv_p2_asm(SnapArgs a, uint3
                 if (kg == 0) red[par][wv][sub * 32 + n] = sm;
             }
             __builtin_amdgcn_sched_barrier(0);
-            wait_tile_landed();
+            dma_wait<MF_SUBS>();   // only the newest tile's requests of this wave may still be in flight
             __syncthreads();
             if (threadIdx.x < MF_TILE) {
                 const uint32_t kk = key0 + threadIdx.x;
@@ -837,7 +791,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void snapkv_p2_asm(SnapArgs a, uint3
                     cs[kk] = sm;
                 }
             }
-            bc = ring_next(bc);
+            bc = KGeo<8>::ring_next(bc);
         }
     }
     wait_all_landed();

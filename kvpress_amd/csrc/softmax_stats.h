@@ -10,12 +10,6 @@
 constexpr float KVP_LOG2E = 1.4426950408889634f;
 constexpr float KVP_NEG_INF = -__builtin_huge_valf();
 
-// order-preserving key <-> float (for atomicMax over floats of any sign)
-__device__ __forceinline__ float key_to_float(uint32_t k) {
-    const uint32_t u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
-    return __uint_as_float(u);
-}
-
 // fold (m2,z2) into (m,z); either side may be the empty partial (m = -inf, z = 0)
 __device__ __forceinline__ void softmax_merge(float& m, float& z, float m2, float z2) {
     if (m2 == KVP_NEG_INF) return;
@@ -24,7 +18,15 @@ __device__ __forceinline__ void softmax_merge(float& m, float& z, float m2, floa
     z = z * exp2f(m - mn) + z2 * exp2f(m2 - mn);
     m = mn;
 }
-
+// butterfly of softmax_merge over the lane distances HI, HI / 2, .., LO: <32, 1> the whole wave, <16, 1> each group of 32 lanes,
+// <32, 32> the single fold across the two lane halves (the MFMA layouts split a row's keys between lane l and lane l ^ 32)
+template <int HI = 32, int LO = 1> __device__ __forceinline__ void wave_softmax_merge(float& m, float& z) {
+#pragma unroll
+    for (int o = HI; o >= LO; o >>= 1) {
+        const float m2 = __shfl_xor(m, o), z2 = __shfl_xor(z, o);
+        softmax_merge(m, z, m2, z2);
+    }
+}
 // a[row] = M + log2(Z) from part_m/part_z [nrows][nchunk]; one wave per row (rows = [.., W] window rows when norm_base is used).
 // pad > 0 (SnapKV's MFMA path, snapkv_internal.h): rows are [.., W] PADDED window rows whose first `pad` are padding: their
 // normaliser becomes +inf (2^(L2 - inf) = 0: they add nothing to a column sum), the real window row of row p is p - pad.
@@ -44,11 +46,7 @@ static __global__ __launch_bounds__(256) void softmax_combine_kernel(const float
     if (row >= nrows) return;
     float m = KVP_NEG_INF, z = 0.f;
     for (uint32_t j = lane; j < nchunk; j += 64) softmax_merge(m, z, part_m[(size_t)row * nchunk + j], part_z[(size_t)row * nchunk + j]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float m2 = __shfl_xor(m, o), z2 = __shfl_xor(z, o);
-        softmax_merge(m, z, m2, z2);
-    }
+    wave_softmax_merge(m, z);
     if (lane == 0) a[row] = softmax_row_normaliser(m, z, row, W, norm_base, pad);
 }
 

@@ -491,7 +491,7 @@ __global__ __launch_bounds__(TR_THREADS) void topk_row_kernel(const float* __res
     int32_t* ob = reinterpret_cast<int32_t*>(lh);
     // (the threshold through an SGPR: otherwise the 2 x PER lane masks of the counting loop above are kept alive across
     // the scan for reuse here, which spills SGPRs)
-    const uint32_t Ts = (uint32_t)__builtin_amdgcn_readfirstlane((int)T);
+    const uint32_t Ts = uni(T);
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
         const bool isg = keys[j] > Ts;

@@ -175,16 +175,6 @@ struct ClusterArgs {
 enum { TC_SCORES = 0, TC_POOL5 = 1, TC_KNORM_BF16 = 2, TC_KNORM_F16 = 3 };
 constexpr int TC_NS = 128;   // sampled keys per row (two-hop form)
 
-template <int DT>
-__device__ __forceinline__ float tc_sumsq16(const uint4& v) {   // = rownorm.hip's sumsq16 (same fma chain)
-    float f[Elem<DT>::PER16];
-    unpack16<DT>(v, f);
-    float a = 0.f;
-#pragma unroll
-    for (int i = 0; i < Elem<DT>::PER16; ++i) a = fmaf(f[i], f[i], a);
-    return a;
-}
-
 // topk_hist_add_bin (topk_internal.h) with a per-lane weight of `w` for the lanes flagged `heavy` and 1 for the others: two rounds of
 // wave-level aggregation, then plain LDS atomics.  Every thread of the wave must call it together.
 __device__ __forceinline__ void tc_hist_add_weighted(uint32_t* lds_hist, uint32_t bin, bool valid, bool heavy, uint32_t w) {
@@ -202,9 +192,6 @@ __device__ __forceinline__ void tc_hist_add_weighted(uint32_t* lds_hist, uint32_
     }
     if (valid) atomicAdd(&lds_hist[bin], heavy ? w : 1u);
 }
-
-// a value that every lane holds identically, moved to a scalar register: branches on it are scalar branches (no saved exec masks)
-__device__ __forceinline__ uint32_t tc_uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
 
 // out-of-range positions carry key 0; real keys are >= 1 (as in topk_row_kernel)
 __device__ __forceinline__ uint32_t tc_key(float f, uint32_t kmask) { return max(float_to_key(f) ^ kmask, 1u); }
@@ -256,7 +243,7 @@ __global__ __launch_bounds__(TR_THREADS) void topk_cluster_kernel(ClusterArgs a)
         constexpr bool KN = MODE == TC_KNORM_BF16 || MODE == TC_KNORM_F16;
         // wave-uniform conditions (scalar branches) instead of thread-index comparisons: the compiler hoists the latter into lane
         // masks that live across the whole kernel and overflow the scalar register file
-        const uint32_t wvu = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        const uint32_t wvu = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (not uni(): on the wave index it changes this kernel's code)
         float smp_f = 0.f;          // SCORES / POOL5: thread t < TC_NS holds sample t
         uint4 smp_v[KN ? TC_NS / 64 : 1];   // KNORM: 16 lanes per sampled row, 64 rows per step
         const uint32_t smp_stride = S / TC_NS;   // S > 16384: >= 64
@@ -298,7 +285,7 @@ __global__ __launch_bounds__(TR_THREADS) void topk_cluster_kernel(ClusterArgs a)
                 constexpr int DT = MODE == TC_KNORM_BF16 ? KVP_BF16 : KVP_F16;
 #pragma unroll
                 for (int u = 0; u < (KN ? TC_NS / 64 : 1); ++u) {
-                    float acc = tc_sumsq16<DT>(smp_v[u]);
+                    float acc = sumsq16<DT>(smp_v[u]);
 #pragma unroll
                     for (int o = 8; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
                     const uint32_t si = u * 64 + (threadIdx.x >> 4);
@@ -336,7 +323,7 @@ __global__ __launch_bounds__(TR_THREADS) void topk_cluster_kernel(ClusterArgs a)
                 if (q == 0 && c == r_hi) swin[1] = xi;
             }
             __syncthreads();
-            const uint32_t Lk = tc_uni(swin[0]), Hk = tc_uni(swin[1]);
+            const uint32_t Lk = uni(swin[0]), Hk = uni(swin[1]);
             while (((Hk >> sft) - (Lk >> sft)) > (uint32_t)(TC_WB - 3)) ++sft;
             wbase = Lk >> sft;
         };
@@ -415,7 +402,7 @@ __global__ __launch_bounds__(TR_THREADS) void topk_cluster_kernel(ClusterArgs a)
                 if (!HIST1 && it == 0) window_setup();   // (the sample's loads are older than this step's: they have landed or land first)
 #pragma unroll
                 for (int u = 0; u < TC_KN_UNROLL; ++u) {
-                    float acc = tc_sumsq16<DT>(v[u]);
+                    float acc = sumsq16<DT>(v[u]);
 #pragma unroll
                     for (int o = 8; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
                     if (lir == 0) {
@@ -514,7 +501,7 @@ __global__ __launch_bounds__(TR_THREADS) void topk_cluster_kernel(ClusterArgs a)
 #pragma unroll
                     for (int i = 0; i < PB; ++i) sum += loc[i];
                     const uint32_t inc = wave_incl_scan(sum), excl = inc - sum;
-                    if (tc_uni((uint32_t)__builtin_amdgcn_readlane((int)inc, 63)) == S) {
+                    if (uni((uint32_t)__builtin_amdgcn_readlane((int)inc, 63)) == S) {
                         if (excl < k && k <= inc) {
                             uint32_t c = excl;
 #pragma unroll
@@ -540,11 +527,11 @@ __global__ __launch_bounds__(TR_THREADS) void topk_cluster_kernel(ClusterArgs a)
             }
             __syncthreads();
             uint32_t d1 = res2[0], k1 = res2[1];
-            d1 = tc_uni(d1);
-            k1 = tc_uni(k1);
+            d1 = uni(d1);
+            k1 = uni(k1);
             // (a poll that gave up: straight to the poison branch -- the workgroups that did see the complete histogram find this one's
             // report in the cluster's flag while they spin at the candidates' barrier, which this one never reaches, and end there too)
-            if (tc_uni(s_fail[0]) != 0) {
+            if (uni(s_fail[0]) != 0) {
                 done = true;
             } else if (d1 >= 1u && d1 <= (uint32_t)(TC_WB - 2)) {
                 // ---- candidates of this slot: keys in bin d1; ngt: keys in higher bins ----------------------------------------
@@ -588,8 +575,8 @@ __global__ __launch_bounds__(TR_THREADS) void topk_cluster_kernel(ClusterArgs a)
                 }
                 __syncthreads();
                 const bool ovf = hdr[(threadIdx.x & (TC_SLOTS - 1)) * 2] == 0xFFFFFFFFu;   // (every wave looks at all 32 records)
-                const bool any_ovf = tc_uni((uint32_t)__syncthreads_or(ovf)) != 0u;
-                if (tc_uni(s_fail[0] | s_fail[1])) {
+                const bool any_ovf = uni((uint32_t)__syncthreads_or(ovf)) != 0u;
+                if (uni(s_fail[0] | s_fail[1])) {
                     done = true;   // poisoned below
                 } else if (!any_ovf) {
                     const uint32_t cnt = hdr[wrec * 2];
@@ -630,8 +617,8 @@ __global__ __launch_bounds__(TR_THREADS) void topk_cluster_kernel(ClusterArgs a)
                             }
                         }
                         __syncthreads();
-                        Tpre |= tc_uni(res2[0]) << lo;
-                        krem = tc_uni(res2[1]);
+                        Tpre |= uni(res2[0]) << lo;
+                        krem = uni(res2[1]);
                         hi = lo;
                     }
                     T = Tpre;
@@ -817,7 +804,7 @@ __global__ __launch_bounds__(TR_THREADS) void topk_cluster_kernel(ClusterArgs a)
         if (slot == 0)
             for (uint32_t j = threadIdx.x; j < a.tail_n; j += TR_THREADS) out[k + j] = (int32_t)(off + a.tail_start + j);
         int32_t* ob = reinterpret_cast<int32_t*>(lh);   // staged: the ranks of one thread are consecutive, the stores below coalesced
-        const uint32_t Ts = (uint32_t)__builtin_amdgcn_readfirstlane((int)T);
+        const uint32_t Ts = uni(T);
 #pragma unroll
         for (int j = 0; j < PER; ++j) {
             const bool isg = keys[j] > Ts;

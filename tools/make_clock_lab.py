@@ -78,7 +78,7 @@ def insert_before(src, anchor, text, nth=0, count=None):
 
 
 def patch_snapkv(src):
-    src = insert_after(src, "typedef float f32x16", STAMP_DECL % dict(nk=2), count=1)
+    src = insert_after(src, "constexpr int MF_THREADS = 512;", STAMP_DECL % dict(nk=2), count=1)
     # pass 1 (asm): begin after the ring declaration, end before the final merge of the two lane halves
     src = insert_after(src, "__shared__ __attribute__((aligned(16))) unsigned char lds[NB * MF_TILEB];", "    kvp_lab_begin(0);", count=1)
     src = insert_before(src, "float mm = m == KVP_NEG_INF ? KVP_NEG_INF : m * c, zz = z;", "    kvp_lab_end(0);", nth=1, count=2)

@@ -18,7 +18,7 @@ ANCHORS = [
     ("        const bool full = kmin != 0u;", 1, "after"),                                       # keys loaded
     ("            uint32_t* whist = fh + 2 * TC_NS;   // (zeroed by window_setup)", 2, "before"),  # (the window is set up inside the key phase)
     ("            // complete when the histogram's total is the row's S keys", 3, "before"),     # window histogram flushed
-    ("            d1 = tc_uni(d1);", 4, "before"),                                               # window digit found (poll complete)
+    ("            d1 = uni(d1);", 4, "before"),                                                  # window digit found (poll complete)
     ("                cluster_barrier(cs, 2, &s_fail[0], true);", 5, "before"),                  # candidate record written
     ("                cluster_barrier(cs, 2, &s_fail[0], true);", 6, "after"),
     ("                const bool ovf = ", 7, "before"),                                          # the row's records in LDS
