@@ -329,6 +329,49 @@ int kvp_merge_values(const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, co
                      int64_t D, double similarity_threshold, double merge_fraction, void* ws, size_t ws_bytes, int32_t* target,
                      float* max_sim, kvp_stream_t stream);
 
+/* ---- CAMPress: per-step attention accumulation (kvpress/presses/cam_press.py:258-283, 326-361) ----------------------------------------
+ * Every decoding step of a layer: a[b,hkv,s] = mean over the G = Hq / Hkv query heads of the group of softmax_s(q_g . k_s / sqrt(D)) over
+ * ALL S keys (the newest token's own key included, :346-348), in float32, and in place
+ *     running[b,hkv,s] = (s < S_prev ? running[b,hkv,s] : 0) + a[b,hkv,s]     for s < S
+ * which is the reference's zero pad of the running sum (:273-281) and its `+=` (:283) without a torch.cat per step; S_prev = 0 is its
+ * first step (:270-271).  q: the PRE-RoPE query of the newest token [B,Hq,1,D]; cos / sin: its row of the position embeddings [Bc,1,D],
+ * Bc = B or 1 (cs_sb = 0 broadcasts); the RoPE is evaluated as in kvp_snapkv_score_rope (:341-344).  k: keys [B,Hkv,S,D] (element
+ * strides).  running: float32 rows of capacity cap >= S (element strides r_sb, r_sh).  D even and <= 256, G <= 16.  S is split over
+ * workgroups (two-pass softmax statistics, combined in a fixed order: bit-identical from run to run, no float atomics).  Workspace:
+ * 4 bytes per (b, query head, key) + O(B * Hq * 256). */
+size_t kvp_cam_attn_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t S);
+int kvp_cam_attn_accumulate(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_sw, const void* cos, const void* sin, int64_t cs_sb,
+                            int64_t cs_sw, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, int dtype, int64_t B, int64_t Hq,
+                            int64_t Hkv, int64_t S, int64_t D, float* running, int64_t r_sb, int64_t r_sh, int64_t cap, int64_t S_prev,
+                            void* ws, size_t ws_bytes, kvp_stream_t stream);
+/* The same when the attention layer returned its weights (cam_press.py:259-265): attn is the last query row, [B,Hq,S] (element strides
+ * a_sb, a_sh, last dim contiguous) in `dtype`; only the group mean (:356-361) and the accumulation run. */
+int kvp_cam_attn_accumulate_row(const void* attn, int64_t a_sb, int64_t a_sh, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S,
+                                float* running, int64_t r_sb, int64_t r_sh, int64_t cap, int64_t S_prev, kvp_stream_t stream);
+
+/* ---- CAMPress: merge plan (kvpress/presses/cam_press.py:144-183) ---------------------------------------------------------------------
+ * kept: the T kept positions, ascending, int32 [B,T]; attn: the running sum, float32 [B,H,>=S] (element strides a_sb, a_sh).  sel, int32
+ * [B,n_sel] ascending, is either the M merge candidates themselves (n_sel == M) or the superset kept + candidates (n_sel == T + M: the
+ * position-order selects of the top T and the top T + M scores; the candidates are then found here, the i-th entry of sel that is not
+ * kept -- no sort or set difference on the host for :144-157).  For candidate i at position p: start[b,i] = #{kept <= p} (searchsorted
+ * right, :159), budget = min(merge_budget, T - start) (:164-169), mean = sum of attn over kept[start .. start + budget) / max(budget, 1)
+ * (:172-176), prob[b,h,i] = attn[b,h,p] / mean with NaN -> 0, +-inf -> 1, clamped to [0, 1] (:179-183).  cand (may be NULL) and start:
+ * int32 [B,M]; prob: float32 [B,H,M], contiguous.  1 <= T <= S, 0 <= M <= S - T, merge_budget > 0. */
+int kvp_cam_merge_plan(const int32_t* kept, const int32_t* sel, int64_t n_sel, const float* attn, int64_t a_sb, int64_t a_sh, int64_t B,
+                       int64_t H, int64_t S, int64_t T, int64_t M, int64_t merge_budget, int32_t* cand, int32_t* start, float* prob,
+                       kvp_stream_t stream);
+
+/* ---- CAMPress: merge and prune (kvpress/presses/cam_press.py:188-213) ----------------------------------------------------------------
+ * New contiguous tensors k_out, v_out [B,H,T,D] and attn_out float32 [B,H,T]: k_out and attn_out are the gathers of k and attn at the
+ * kept positions (:205-213); v_out[b,h,t] = v[kept[t]] + sum over the candidates i with start[b,i] <= t < start[b,i] + budget_i of
+ * mask[b,h,i] / budget_i * v[cand[i]] (:189-202), where start is kvp_cam_merge_plan's and mask float32 [B,H,M] (the Bernoulli draw of
+ * prob, :186).  The sum runs in float32 in ascending candidate order and is rounded to the dtype once; a row without contributors
+ * keeps its bits.  k, v and attn are NOT written (the reference scatter-adds into the cache's values in place, :202).  D <= 256. */
+int kvp_cam_merge_prune(const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* v, int64_t v_sb, int64_t v_sh, int64_t v_ss,
+                        const float* attn, int64_t a_sb, int64_t a_sh, const int32_t* kept, const int32_t* cand, const int32_t* start,
+                        const float* mask, int dtype, int64_t B, int64_t H, int64_t S, int64_t T, int64_t M, int64_t D,
+                        int64_t merge_budget, void* k_out, void* v_out, float* attn_out, kvp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

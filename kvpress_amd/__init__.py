@@ -8,6 +8,7 @@ include/kvpress_hip.h; there is no CPU or pure-PyTorch fallback.
 """
 from kvpress_amd.presses.adakv_press import AdaKVPress
 from kvpress_amd.presses.base_press import BasePress
+from kvpress_amd.presses.cam_press import CAMPress
 from kvpress_amd.presses.chunk_press import ChunkPress
 from kvpress_amd.presses.compactor_press import CompactorPress
 from kvpress_amd.presses.composed_press import ComposedPress
@@ -33,18 +34,18 @@ from kvpress_amd.presses.tova_press import TOVAPress
 __version__ = "0.1.0"
 # the path (a), the scorers that reuse its kernels (f-2), the selection wrappers (f-3), the decode-time step (f-4), the
 # pipeline (f-1); plus four tiny host-only presses the reference's own test fixtures for those rows are built from (Composed, PerLayer,
-# Random, StreamingLLM); plus the Compactor family (NonCausalAttn, LeverageScore, Compactor) and MergingPress.  Presses outside that scope that still have kernels here live in kvpress_amd.contrib.
+# Random, StreamingLLM); plus the Compactor family (NonCausalAttn, LeverageScore, Compactor), MergingPress and CAMPress.  Presses outside that scope that still have kernels here live in kvpress_amd.contrib.
 __all__ = ["BasePress", "ScorerPress", "KnormPress", "SnapKVPress", "ExpectedAttentionPress", "PyramidKVPress", "TOVAPress", "KeyDiffPress", "QFilterPress",
            "CURPress", "FinchPress", "ChunkPress", "KeyRerotationPress", "AdaKVPress", "DecodingPress", "CompressionRatioDecodingPress", "PrefillDecodingPress",
            "ComposedPress", "PerLayerCompressionPress", "RandomPress", "StreamingLLMPress", "KVPressTextGenerationPipeline",
-           "NonCausalAttnPress", "LeverageScorePress", "CompactorPress", "MergingPress"]
+           "NonCausalAttnPress", "LeverageScorePress", "CompactorPress", "MergingPress", "CAMPress"]
 
 
 # The reference exports every press at top level (kvpress/__init__.py:7-49).  The five out-of-scope presses that exist here resolve
 # lazily to kvpress_amd.contrib (so `from kvpress_amd import ThinKPress` works like `from kvpress import ThinKPress` without the hot-path
 # package importing its contrib sub-package); the reference's other presses are NOT part of this package and say so.
 _CONTRIB = ("BlockPress", "ChunkKVPress", "LagKVPress", "ObservedAttentionPress", "ThinKPress")
-_NOT_BUILT = ("CAMPress", "CapPress", "CriticalAdaKVPress", "CriticalKVPress", "DMSPress", "DuoAttentionPress",
+_NOT_BUILT = ("CapPress", "CriticalAdaKVPress", "CriticalKVPress", "DMSPress", "DuoAttentionPress",
               "ExpectedAttentionStatsPress", "FastKVzipPress", "KVComposePress", "KVzapPress", "KVzipPress", "LUKVPress",
               "RestoreKVPress", "SimLayerKVPress")
 

@@ -97,6 +97,14 @@ SIGNATURES = {
     "kvp_merge_workspace_bytes": (c_size_t, [_I64] * 5),
     "kvp_merge_values": (c_int, [c_void_p, _I64, _I64, _I64, c_void_p, _I64, _I64, _I64, c_void_p, c_void_p, c_void_p, c_int, _I64, _I64, _I64,
                                  _I64, _I64, c_double, c_double, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "kvp_cam_attn_workspace_bytes": (c_size_t, [_I64] * 4),
+    "kvp_cam_attn_accumulate": (c_int, [c_void_p, _I64, _I64, _I64, c_void_p, c_void_p, _I64, _I64, c_void_p, _I64, _I64, _I64, c_int,
+                                        _I64, _I64, _I64, _I64, _I64, c_void_p, _I64, _I64, _I64, _I64, c_void_p, c_size_t, c_void_p]),
+    "kvp_cam_attn_accumulate_row": (c_int, [c_void_p, _I64, _I64, c_int, _I64, _I64, _I64, _I64, c_void_p, _I64, _I64, _I64, _I64, c_void_p]),
+    "kvp_cam_merge_plan": (c_int, [c_void_p, c_void_p, _I64, c_void_p, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
+    "kvp_cam_merge_prune": (c_int, [c_void_p, _I64, _I64, _I64, c_void_p, _I64, _I64, _I64, c_void_p, _I64, _I64, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_int, _I64, _I64, _I64, _I64, _I64, _I64, _I64, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 # include/kvpress_hip_lab.h: measurement / test aids of the same library (bench.py, tools/, the select's residency tests)
 LAB_SIGNATURES = {
@@ -746,6 +754,83 @@ def merge_values_(keys: torch.Tensor, values: torch.Tensor, kept_idx: torch.Tens
         _call("kvp_merge_values", *_tensor(keys), *_tensor(values), _p(kept_idx), _p(k_out), _p(v_out), _DTYPES[dt], B, H, S, n, D,
               float(threshold), float(fraction), _p(ws), ws.numel(), _p(target), _p(max_sim), _stream(keys))
     return v_out
+
+
+# CAMPress (cam_press.py:124-361)
+def _cam_running(running: torch.Tensor, B: int, Hkv: int, S: int, s_prev: int):
+    assert running.dtype == torch.float32 and running.is_cuda and running.dim() == 3 and running.stride(2) == 1, (running.shape, running.dtype)
+    assert tuple(running.shape[:2]) == (B, Hkv) and running.shape[2] >= S and 0 <= s_prev <= S, (running.shape, (B, Hkv, S), s_prev)
+    return (*_tensor(running, 2), running.shape[2], int(s_prev))
+
+
+def cam_attn_accumulate_(q_pre: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, keys: torch.Tensor, running: torch.Tensor,
+                         s_prev: int) -> torch.Tensor:
+    """In place: running[b,h,s] = (s < s_prev ? running[b,h,s] : 0) + the newest token's attention over all S keys, averaged over the
+    query heads of kv head h (cam_press.py:258-283, 326-361).  q_pre: its PRE-RoPE query [B,Hq,1,D]; cos / sin: its row [1 or B, 1, D];
+    keys [B,Hkv,S,D]; running: float32 [B,Hkv,cap >= S]."""
+    keys = _rows(keys)
+    q_pre, B, Hq, Hkv, S, W, D = _queries(q_pre, keys)
+    assert W == 1, q_pre.shape
+    cos, sin = _rotary(cos, sin, keys.dtype, (B, 1, D))
+    with _on_device(keys.device):
+        ws = _ws(_ws_bytes("kvp_cam_attn_workspace_bytes", B, Hq, Hkv, S), keys)
+        _call("kvp_cam_attn_accumulate", *_tensor(q_pre), *_tables(cos, sin), *_tensor(keys), _DTYPES[keys.dtype], B, Hq, Hkv, S, D,
+              *_cam_running(running, B, Hkv, S, s_prev), _p(ws), ws.numel(), _stream(keys))
+    return running
+
+
+def cam_attn_accumulate_row_(attn_row: torch.Tensor, running: torch.Tensor, s_prev: int) -> torch.Tensor:
+    """The same from the attention row the layer returned: attn_row [B,Hq,S] (the last query row of the weights, cam_press.py:259-263)."""
+    attn_row = _rows(attn_row)
+    B, Hq, S = attn_row.shape
+    Hkv = running.shape[1]
+    with _on_device(attn_row.device):
+        _call("kvp_cam_attn_accumulate_row", *_tensor(attn_row, 2), _DTYPES[attn_row.dtype], B, Hq, Hkv, S,
+              *_cam_running(running, B, Hkv, S, s_prev), _stream(attn_row))
+    return running
+
+
+def _cam_lists(kept: torch.Tensor, cand: torch.Tensor, running: torch.Tensor, S: int):
+    B, T = kept.shape
+    M = cand.shape[1]
+    for t in (kept, cand):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda and t.shape[0] == B, (t.shape, t.dtype)
+    assert running.dtype == torch.float32 and running.dim() == 3 and running.stride(2) == 1 and running.shape[0] == B and running.shape[2] >= S
+    return B, running.shape[1], T, M
+
+
+def cam_merge_plan(kept: torch.Tensor, sel: torch.Tensor, running: torch.Tensor, S: int, merge_budget: int, n_cand: Optional[int] = None):
+    """(cand, start int32 [B,M], prob float32 [B,H,M]) of the M merge candidates against the kept positions [B,T] and the running
+    attention sum [B,H,>=S] (cam_press.py:144-183).  ``sel`` (int32, ascending) holds the candidates themselves, [B,M], or -- with
+    ``n_cand = M`` -- kept and candidates together, [B,T+M]: the library then finds the candidates."""
+    B, H, T, N = _cam_lists(kept, sel, running, S)
+    M = N if n_cand is None else int(n_cand)
+    assert N in (M, T + M), (N, T, M)
+    cand = torch.empty((B, M), dtype=torch.int32, device=kept.device)
+    start = torch.empty((B, M), dtype=torch.int32, device=kept.device)
+    prob = torch.empty((B, H, M), dtype=torch.float32, device=kept.device)
+    with _on_device(kept.device):
+        _call("kvp_cam_merge_plan", _p(kept), _p(sel), N, *_tensor(running, 2), B, H, int(S), T, M, int(merge_budget), _p(cand), _p(start),
+              _p(prob), _stream(kept))
+    return cand, start, prob
+
+
+def cam_merge_prune(keys: torch.Tensor, values: torch.Tensor, running: torch.Tensor, kept: torch.Tensor, cand: torch.Tensor,
+                    start: torch.Tensor, mask: torch.Tensor, merge_budget: int):
+    """(K', V' [B,H,T,D], A' float32 [B,H,T]): the gathers at the kept positions, V' with the masked candidates' values spread over
+    their windows (cam_press.py:188-213).  New tensors: keys, values and running are not written."""
+    keys, values, B, H, S, D = _kv(keys, values)
+    Bk, Hr, T, M = _cam_lists(kept, cand, running, S)
+    assert (Bk, Hr) == (B, H) and tuple(start.shape) == (B, M) and start.dtype == torch.int32 and start.is_contiguous()
+    mask = mask.to(torch.float32).contiguous()
+    assert tuple(mask.shape) == (B, H, M), (mask.shape, (B, H, M))
+    ko = torch.empty((B, H, T, D), dtype=keys.dtype, device=keys.device)
+    vo = torch.empty_like(ko)
+    ao = torch.empty((B, H, T), dtype=torch.float32, device=keys.device)
+    with _on_device(keys.device):
+        _call("kvp_cam_merge_prune", *_tensor(keys), *_tensor(values), *_tensor(running, 2), _p(kept), _p(cand), _p(start), _p(mask),
+              _DTYPES[keys.dtype], B, H, S, T, M, D, int(merge_budget), _p(ko), _p(vo), _p(ao), _stream(keys))
+    return ko, vo, ao
 
 
 # ---- the q_proj eligibility logic ---------------------------------------------------------------------------------------------------

@@ -27,6 +27,19 @@ def _kv_len(cache, layer_idx: int) -> int:
     return cache.get_seq_length(layer_idx) if _is_quantized(cache) else cache.layers[layer_idx].keys.shape[2]
 
 
+def _write_back(cache, cache_layer, keys: torch.Tensor, values: torch.Tensor) -> None:
+    """Store the compressed keys / values as the layer's cache (decoding_press.py:180-189; a QuantizedCache layer re-quantises them)."""
+    if _is_quantized(cache):
+        cache_layer._quantized_keys = cache_layer._quantize(keys, axis=cache_layer.axis_key)
+        cache_layer._quantized_values = cache_layer._quantize(values, axis=cache_layer.axis_value)
+        cache_layer.keys = torch.zeros(0, dtype=keys.dtype, device=keys.device)
+        cache_layer.values = torch.zeros(0, dtype=keys.dtype, device=keys.device)
+        cache_layer.cumulative_length = keys.shape[2]
+    else:
+        cache_layer.keys = keys
+        cache_layer.values = values
+
+
 @dataclass
 class DecodingPress(BasePress):
     """Parameters
@@ -113,15 +126,7 @@ class DecodingPress(BasePress):
             attentions = output[1] if isinstance(output, (tuple, list)) and len(output) > 1 and output[1] is not None else None
             buffered = torch.cat(self.hidden_states_buffer[layer_idx], dim=1)
             keys, values = self.compress(module, buffered, keys, values, attentions, kwargs)
-            if _is_quantized(cache):
-                cache_layer._quantized_keys = cache_layer._quantize(keys, axis=cache_layer.axis_key)
-                cache_layer._quantized_values = cache_layer._quantize(values, axis=cache_layer.axis_value)
-                cache_layer.keys = torch.zeros(0, dtype=keys.dtype, device=keys.device)
-                cache_layer.values = torch.zeros(0, dtype=keys.dtype, device=keys.device)
-                cache_layer.cumulative_length = keys.shape[2]
-            else:
-                cache_layer.keys = keys
-                cache_layer.values = values
+            _write_back(cache, cache_layer, keys, values)
             self.layer_step_counts[layer_idx] = 0
             self.hidden_states_buffer[layer_idx] = []      # buffer and cache must describe the same tokens
 
