@@ -28,20 +28,20 @@ int64_t cam_chunk(int64_t R, int64_t S) {
     return std::max<int64_t>(64, (c + 63) / 64 * 64);
 }
 
-struct CamLayout {
+struct CamWs {
     int64_t chunk, nchunk;
-    size_t logits, pm, pz, total;
+    float *logits, *pm, *pz;   // [B*Hq][S], [B*Hq][nchunk] twice
+    size_t total;
 };
-CamLayout cam_layout(int64_t B, int64_t Hq, int64_t Hkv, int64_t S) {
-    CamLayout L;
+CamWs cam_ws(void* ws, int64_t B, int64_t Hq, int64_t Hkv, int64_t S) {
+    CamWs L;
     L.chunk = cam_chunk(B * Hkv, S);
     L.nchunk = (S + L.chunk - 1) / L.chunk;
-    size_t off = 0;
-    auto take = [&](size_t n) { const size_t o = off; off = kvp_align_up(off + n, 256); return o; };
-    L.logits = take((size_t)B * Hq * S * 4);
-    L.pm = take((size_t)B * Hq * L.nchunk * 4);
-    L.pz = take((size_t)B * Hq * L.nchunk * 4);
-    L.total = off;
+    KvpArena ar(ws);
+    L.logits = ar.take<float>((size_t)B * Hq * S);
+    L.pm = ar.take<float>((size_t)B * Hq * L.nchunk);
+    L.pz = ar.take<float>((size_t)B * Hq * L.nchunk);
+    L.total = ar.bytes();
     return L;
 }
 
@@ -373,10 +373,9 @@ __global__ __launch_bounds__(CT) void cam_prune_kernel(const typename Elem<DT>::
     }
 }
 
-bool cam_vec_ok(int dtype, int64_t D, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss) {
-    const int per = dtype == KVP_F32 ? 4 : 8;
-    if (D % per != 0 || D / per > 64 || ((uintptr_t)k & 15)) return false;
-    return (k_sb % per == 0) && (k_sh % per == 0) && (k_ss % per == 0);
+bool cam_vec_ok(int dtype, int64_t D, KvpRows k) {
+    const int per = 16 / kvp_elem_size(dtype);
+    return D % per == 0 && D / per <= 64 && k.aligned(16, kvp_elem_size(dtype));
 }
 
 template <int DT>
@@ -407,7 +406,7 @@ bool cam_running_ok(int64_t B, int64_t Hkv, int64_t S, int64_t r_sb, int64_t r_s
 // ================================================================================================================================
 extern "C" size_t kvp_cam_attn_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t S) {
     if (B < 1 || Hq < 1 || Hkv < 1 || S < 1 || Hq % Hkv != 0) return 0;
-    return cam_layout(B, Hq, Hkv, S).total;
+    return cam_ws(nullptr, B, Hq, Hkv, S).total;
 }
 
 extern "C" int kvp_cam_attn_accumulate(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_sw, const void* cosp, const void* sinp,
@@ -416,6 +415,7 @@ extern "C" int kvp_cam_attn_accumulate(const void* q, int64_t q_sb, int64_t q_sh
                                        int64_t cap, int64_t S_prev, void* ws, size_t ws_bytes, kvp_stream_t stream) {
     (void)q_sw;   // one query row
     (void)cs_sw;
+    const KvpRows kr{k, k_sb, k_sh, k_ss};
     KVP_CHECK_DTYPE("kvp_cam_attn_accumulate", dtype);
     KVP_CHECK_ARG(B >= 1 && Hq >= 1 && Hkv >= 1 && S >= 1 && D >= 2 && Hq % Hkv == 0, "kvp_cam_attn_accumulate: bad shape");
     KVP_CHECK_ARG(D % 2 == 0 && D <= CAM_MAX_D, "kvp_cam_attn_accumulate: head size %lld is odd or > 256", (long long)D);
@@ -423,7 +423,7 @@ extern "C" int kvp_cam_attn_accumulate(const void* q, int64_t q_sb, int64_t q_sh
     KVP_CHECK_ARG(S < ((int64_t)1 << 31) && B < 65536 && Hkv < 32768, "kvp_cam_attn_accumulate: bad shape (S, B or Hkv too large)");
     KVP_CHECK_ARG(cam_running_ok(B, Hkv, S, r_sb, r_sh, cap, S_prev), "kvp_cam_attn_accumulate: bad running sum (cap < S, S_prev outside [0, S] or overlapping rows)");
     KVP_CHECK_ARG(q && cosp && sinp && k && running, "kvp_cam_attn_accumulate: null pointer");
-    const CamLayout L = cam_layout(B, Hq, Hkv, S);
+    const CamWs L = cam_ws(ws, B, Hq, Hkv, S);
     if (int rc = kvp_check_workspace("kvp_cam_attn_accumulate", ws, ws_bytes, L.total)) return rc;
     hipStream_t st = (hipStream_t)stream;
     CamAttnArgs a;
@@ -434,10 +434,8 @@ extern "C" int kvp_cam_attn_accumulate(const void* q, int64_t q_sb, int64_t q_sh
     a.gsub = (a.G + a.nsub - 1) / a.nsub;
     a.S = S; a.chunk = L.chunk; a.nchunk = L.nchunk;
     a.scale = (float)(1.4426950408889634 / sqrt((double)D));
-    a.logits = (float*)((char*)ws + L.logits);
-    a.pm = (float*)((char*)ws + L.pm);
-    a.pz = (float*)((char*)ws + L.pz);
-    const bool vec = cam_vec_ok(dtype, D, k, k_sb, k_sh, k_ss);
+    a.logits = L.logits; a.pm = L.pm; a.pz = L.pz;
+    const bool vec = cam_vec_ok(dtype, D, kr);
     KVP_DISPATCH_DTYPE(dtype, if (int rc = cam_attn_run<DT>(a, B, Hkv, vec, st)) return rc);
     const dim3 grid((unsigned)((S + CT - 1) / CT), (unsigned)Hkv, (unsigned)B);
     KVP_LAUNCH("cam_accumulate", st,
@@ -496,7 +494,7 @@ extern "C" int kvp_cam_merge_prune(const void* k, int64_t k_sb, int64_t k_sh, in
     hipStream_t st = (hipStream_t)stream;
     const int bm = (int)std::min<int64_t>(merge_budget, T);
     const dim3 grid((unsigned)((T + CT / 64 - 1) / (CT / 64)), (unsigned)H, (unsigned)B);
-    const bool kvec = cam_vec_ok(dtype, D, k, k_sb, k_sh, k_ss) && !((uintptr_t)k_out & 15);
+    const bool kvec = cam_vec_ok(dtype, D, {k, k_sb, k_sh, k_ss}) && !((uintptr_t)k_out & 15);
     KVP_DISPATCH_DTYPE(dtype, using T_ = typename Elem<DT>::T;
                        KVP_LAUNCH("cam_prune", st,
                                   cam_prune_kernel<DT><<<grid, CT, 0, st>>>((const T_*)k, k_sb, k_sh, k_ss, (const T_*)v, v_sb, v_sh, v_ss, attn, a_sb,

@@ -185,11 +185,8 @@ extern "C" int kvp_occupy_cus(int blocks, int threads, int lds_bytes, int spin_u
     KVP_CHECK_ARG(blocks >= 1 && blocks <= 65535 && threads >= 64 && threads <= 1024 && threads % 64 == 0 && lds_bytes >= 0 &&
                       lds_bytes <= 160 * 1024 && spin_us >= 1 && spin_us <= 200000,
                   "occupy_cus: bad arguments");
-    if (lds_bytes > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(occupy_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) {
-        kvp_set_error("occupy_cus: cannot raise the dynamic LDS limit to %d", lds_bytes);
-        return KVP_EHIP;
-    }
+    if (lds_bytes > 64 * 1024)
+        if (int rc = kvp_raise_dynamic_lds("occupy_cus", occupy_kernel, (size_t)lds_bytes)) return rc;
     occupy_kernel<<<blocks, threads, (size_t)std::max(lds_bytes, 16), stream>>>((uint32_t)spin_us * 100u);
     KVP_CHECK_LAUNCH("occupy_cus");
     return KVP_OK;

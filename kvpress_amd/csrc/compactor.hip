@@ -635,7 +635,10 @@ struct ZsWs {
     double* part;
     double* part2;
 };
-constexpr size_t ZS_BYTES = 2 * ZS_BLOCKS * sizeof(double);
+ZsWs zs_take(KvpArena& ar) {
+    double* p = ar.take<double>(2 * ZS_BLOCKS);
+    return {p, p + ZS_BLOCKS};
+}
 
 int zscore_launch(const float* in, float* raw, int64_t n, int64_t S, int pool, float* z, ZsWs w, hipStream_t st) {
     KVP_LAUNCH("cpt_zs_sum", st, zs_sum_kernel<<<ZS_BLOCKS, GEN_THREADS, 0, st>>>(in, raw, n, S, pool, w.part));
@@ -648,104 +651,120 @@ int zscore_launch(const float* in, float* raw, int64_t n, int64_t S, int pool, f
     return KVP_OK;
 }
 
-size_t nc_ws_bytes(int64_t B, int64_t Hkv, int64_t S) {
-    const size_t plane = kvp_align_up((size_t)(B * Hkv * S) * sizeof(float), 256);
-    return 2 * plane + ZS_BYTES;
+// non-causal attention workspace
+struct NcWs {
+    float *tmp, *raw;   // [B*Hkv*S] each
+    ZsWs zs;
+    size_t total;
+};
+NcWs nc_ws(void* ws, int64_t B, int64_t Hkv, int64_t S) {
+    NcWs w;
+    KvpArena ar(ws);
+    w.tmp = ar.take<float>((size_t)(B * Hkv * S));
+    w.raw = ar.take<float>((size_t)(B * Hkv * S));
+    w.zs = zs_take(ar);
+    w.total = ar.bytes();
+    return w;
 }
 
+// the tensors and sizes of one kvp_ncattn_score call
+struct NcCall {
+    KvpRows q, k, v;
+    KvpRope r;
+    int Hkv, G, S, C, D;
+    float* tmp;
+};
+
 // KVP_NCATTN_GENERIC=1 sends every shape to the generic kernel (tests of that path on the shapes the MFMA kernel takes)
-bool nc_mfma_ok(int dtype, int64_t D, int64_t C, int64_t G, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, int64_t q_sh,
-                int64_t q_ss, int64_t cs_ss, int64_t v_ss) {
-    if (dtype == KVP_F32 || G > 16 || C % 32 != 0 || C > 512) return false;
-    if (!(D == 64 || D == 96 || D == 128 || D == 256)) return false;
+bool nc_mfma_ok(const NcCall& c, int dtype) {
+    if (dtype == KVP_F32 || c.G > 16 || c.C % 32 != 0 || c.C > 512) return false;
+    if (!(c.D == 64 || c.D == 96 || c.D == 128 || c.D == 256)) return false;
     if (kvp_env_int("KVP_NCATTN_GENERIC", 0)) return false;
     // row / head strides as 32-bit numbers inside the kernel (one chunk of rows from a per-block base pointer)
-    const int64_t lim = (int64_t)1 << 30;
-    if (std::abs(q_sh) * 16 >= lim || std::abs(q_ss) * C >= lim || std::abs(cs_ss) * C >= lim || std::abs(k_ss) * C >= lim || std::abs(v_ss) >= lim)
+    const int64_t lim = (int64_t)1 << 30, C = c.C;
+    if (std::abs(c.q.sh) * 16 >= lim || std::abs(c.q.ss) * C >= lim || std::abs(c.r.sw) * C >= lim || std::abs(c.k.ss) * C >= lim || std::abs(c.v.ss) >= lim)
         return false;
     // 16-byte key fragments straight from the cache rows
-    return ((uintptr_t)k % 16 == 0) && k_sb % 8 == 0 && k_sh % 8 == 0 && k_ss % 8 == 0;
+    return c.k.aligned(16, 2);
 }
 
 template <int DT, int D>
-void nc_mfma_launch(dim3 grid, hipStream_t st, const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const void* cs, const void* sn,
-                    int64_t cs_sb, int64_t cs_ss, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* v, int64_t v_sb,
-                    int64_t v_sh, int64_t v_ss, int Hkv, int G, int S, int C, float* tmp) {
+void nc_mfma_launch(const NcCall& c, dim3 grid, hipStream_t st) {
     using T = typename Elem<DT>::T;
     KVP_LAUNCH("ncattn_mfma", st,
-               ncattn_mfma_kernel<DT, D><<<grid, NC_THREADS, 0, st>>>((const T*)q, q_sb, (int)q_sh, (int)q_ss, (const T*)cs, (const T*)sn, cs_sb,
-                                                                     (int)cs_ss, (const T*)k, k_sb, k_sh, (int)k_ss, (const T*)v, v_sb, v_sh,
-                                                                     (int)v_ss, Hkv, G, S, C, tmp));
+               ncattn_mfma_kernel<DT, D><<<grid, NC_THREADS, 0, st>>>((const T*)c.q.p, c.q.sb, (int)c.q.sh, (int)c.q.ss, (const T*)c.r.cosp, (const T*)c.r.sinp, c.r.sb,
+                                                                     (int)c.r.sw, (const T*)c.k.p, c.k.sb, c.k.sh, (int)c.k.ss, (const T*)c.v.p, c.v.sb, c.v.sh,
+                                                                     (int)c.v.ss, c.Hkv, c.G, c.S, c.C, c.tmp));
 }
 
 template <int DT>
-int nc_run(bool mfma, dim3 grid, hipStream_t st, const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const void* cs, const void* sn,
-           int64_t cs_sb, int64_t cs_ss, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* v, int64_t v_sb, int64_t v_sh,
-           int64_t v_ss, int Hkv, int G, int S, int C, int D, float* tmp) {
+int nc_run(const NcCall& c, bool mfma, dim3 grid, hipStream_t st) {
     using T = typename Elem<DT>::T;
     if constexpr (DT != KVP_F32) {
         if (mfma) {
-            switch (D) {
-                case 64: nc_mfma_launch<DT, 64>(grid, st, q, q_sb, q_sh, q_ss, cs, sn, cs_sb, cs_ss, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, Hkv, G, S, C, tmp); break;
-                case 96: nc_mfma_launch<DT, 96>(grid, st, q, q_sb, q_sh, q_ss, cs, sn, cs_sb, cs_ss, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, Hkv, G, S, C, tmp); break;
-                case 128: nc_mfma_launch<DT, 128>(grid, st, q, q_sb, q_sh, q_ss, cs, sn, cs_sb, cs_ss, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, Hkv, G, S, C, tmp); break;
-                default: nc_mfma_launch<DT, 256>(grid, st, q, q_sb, q_sh, q_ss, cs, sn, cs_sb, cs_ss, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, Hkv, G, S, C, tmp); break;
+            switch (c.D) {
+                case 64: nc_mfma_launch<DT, 64>(c, grid, st); break;
+                case 96: nc_mfma_launch<DT, 96>(c, grid, st); break;
+                case 128: nc_mfma_launch<DT, 128>(c, grid, st); break;
+                default: nc_mfma_launch<DT, 256>(c, grid, st); break;
             }
             KVP_CHECK_LAUNCH("ncattn_mfma_kernel");
             return KVP_OK;
         }
     }
     KVP_LAUNCH("ncattn_generic", st,
-               ncattn_generic_kernel<DT><<<grid, GEN_THREADS, D * sizeof(float), st>>>((const T*)q, q_sb, q_sh, q_ss, (const T*)cs, (const T*)sn,
-                                                                                       cs_sb, cs_ss, (const T*)k, k_sb, k_sh, k_ss, (const T*)v,
-                                                                                       v_sb, v_sh, v_ss, Hkv, G, S, C, D, tmp));
+               ncattn_generic_kernel<DT><<<grid, GEN_THREADS, c.D * sizeof(float), st>>>((const T*)c.q.p, c.q.sb, c.q.sh, c.q.ss, (const T*)c.r.cosp, (const T*)c.r.sinp,
+                                                                                         c.r.sb, c.r.sw, (const T*)c.k.p, c.k.sb, c.k.sh, c.k.ss, (const T*)c.v.p,
+                                                                                         c.v.sb, c.v.sh, c.v.ss, c.Hkv, c.G, c.S, c.C, c.D, c.tmp));
     KVP_CHECK_LAUNCH("ncattn_generic_kernel");
     return KVP_OK;
 }
 
-// leverage workspace layout
-struct LvLayout {
+// leverage workspace
+struct LvWs {
     int nb, nb2;
-    size_t mpart, gpart, A, Y, minv, status, raw, zs, total;
+    float *mpart, *gpart;
+    double *A, *Y;
+    float* minv;
+    int* status;
+    float* raw;
+    ZsWs zs;
+    size_t total;
 };
-LvLayout lv_layout(int64_t B, int64_t H, int64_t S, int64_t D, int64_t ks) {
-    LvLayout L;
+LvWs lv_ws(void* ws, int64_t B, int64_t H, int64_t S, int64_t D, int64_t ks) {
+    LvWs w;
     const int64_t BH = B * H;
-    L.nb = (int)std::max<int64_t>(1, std::min<int64_t>((S + 1023) / 1024, 64));
+    w.nb = (int)std::max<int64_t>(1, std::min<int64_t>((S + 1023) / 1024, 64));
     const int64_t ntiles = (S + LV_TILE - 1) / LV_TILE;
     const int64_t budget = (int64_t)8 << 20;   // partial Gram matrices: at most ~8 MiB (or one per head)
-    L.nb2 = (int)std::max<int64_t>(1, std::min<int64_t>({(ntiles + 7) / 8, (int64_t)64, budget / std::max<int64_t>(1, BH * ks * ks * 4)}));
-    size_t off = 0;
-    auto take = [&](size_t n) { const size_t o = off; off = kvp_align_up(off + n, 256); return o; };
-    L.mpart = take((size_t)BH * L.nb * D * sizeof(float));
-    L.gpart = take((size_t)BH * L.nb2 * ks * ks * sizeof(float));
-    L.A = take((size_t)BH * ks * ks * sizeof(double));
-    L.Y = take((size_t)BH * ks * ks * sizeof(double));
-    L.minv = take((size_t)BH * ks * ks * sizeof(float));
-    L.status = take((size_t)BH * sizeof(int));
-    L.raw = take((size_t)BH * S * sizeof(float));
-    L.zs = take(ZS_BYTES);
-    L.total = off;
-    return L;
+    w.nb2 = (int)std::max<int64_t>(1, std::min<int64_t>({(ntiles + 7) / 8, (int64_t)64, budget / std::max<int64_t>(1, BH * ks * ks * 4)}));
+    KvpArena ar(ws);
+    w.mpart = ar.take<float>((size_t)BH * w.nb * D);
+    w.gpart = ar.take<float>((size_t)BH * w.nb2 * ks * ks);
+    w.A = ar.take<double>((size_t)BH * ks * ks);
+    w.Y = ar.take<double>((size_t)BH * ks * ks);
+    w.minv = ar.take<float>((size_t)BH * ks * ks);
+    w.status = ar.take<int>((size_t)BH);
+    w.raw = ar.take<float>((size_t)BH * S);
+    w.zs = zs_take(ar);
+    w.total = ar.bytes();
+    return w;
 }
 
+// phi [B,H,D,ks]: the sketch, element strides of its three outer dims in p.sb, p.sh, p.ss
 template <int DT>
-void lv_run(const LvLayout& L, char* ws, hipStream_t st, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* phi,
-            int64_t p_sb, int64_t p_sh, int64_t p_sd, int B, int H, int S, int D, int ks, float* raw) {
+void lv_run(const LvWs& w, hipStream_t st, KvpRows k, KvpRows p, int B, int H, int S, int D, int ks, float* raw) {
     using T = typename Elem<DT>::T;
-    float* mpart = (float*)(ws + L.mpart);
-    float* gpart = (float*)(ws + L.gpart);
-    float* minv = (float*)(ws + L.minv);
-    KVP_LAUNCH("lv_mean", st, lv_mean_kernel<DT><<<dim3(L.nb, B * H), LV_THREADS, 0, st>>>((const T*)k, k_sb, k_sh, k_ss, H, S, D, L.nb, mpart));
+    KVP_LAUNCH("lv_mean", st, lv_mean_kernel<DT><<<dim3(w.nb, B * H), LV_THREADS, 0, st>>>((const T*)k.p, k.sb, k.sh, k.ss, H, S, D, w.nb, w.mpart));
     // entries per thread of an RB-row block of G: RB * ks / 256 (<= 16), rounded up to the next instantiated count; as few row blocks as that allows
     // (every row block recomputes the sketch of its tokens)
     const int RB = std::max(1, std::min(ks, 16 * LV_THREADS / ks));
     const int ntiles = (S + LV_TILE - 1) / LV_TILE;
-    const dim3 gg(L.nb2, B * H, (ks + RB - 1) / RB);
+    const dim3 gg(w.nb2, B * H, (ks + RB - 1) / RB);
     const int nu = (RB * ks + LV_THREADS - 1) / LV_THREADS;
 #define LV_GRAM(NU_)                                                                                                                     \
-    KVP_LAUNCH("lv_gram", st, lv_gram_kernel<DT, NU_><<<gg, LV_THREADS, 0, st>>>((const T*)k, k_sb, k_sh, k_ss, (const T*)phi, p_sb, p_sh, \
-                                                                                p_sd, H, S, D, ks, L.nb, mpart, L.nb2, RB, gpart))
+    KVP_LAUNCH("lv_gram", st, lv_gram_kernel<DT, NU_><<<gg, LV_THREADS, 0, st>>>((const T*)k.p, k.sb, k.sh, k.ss, (const T*)p.p, p.sb, p.sh, \
+                                                                                p.ss, H, S, D, ks, w.nb, w.mpart, w.nb2, RB, w.gpart))
     if (nu <= 2) LV_GRAM(2);
     else if (nu <= 4) LV_GRAM(4);
     else if (nu <= 6) LV_GRAM(6);
@@ -754,12 +773,10 @@ void lv_run(const LvLayout& L, char* ws, hipStream_t st, const void* k, int64_t 
     else if (nu <= 12) LV_GRAM(12);
     else LV_GRAM(16);
 #undef LV_GRAM
-    KVP_LAUNCH("lv_chol", st,
-               lv_chol_kernel<<<B * H, LV_THREADS, 0, st>>>(gpart, L.nb2, ks, (double*)(ws + L.A), (double*)(ws + L.Y), minv, (int*)(ws + L.status)));
+    KVP_LAUNCH("lv_chol", st, lv_chol_kernel<<<B * H, LV_THREADS, 0, st>>>(w.gpart, w.nb2, ks, w.A, w.Y, w.minv, w.status));
     KVP_LAUNCH("lv_score", st,
-               lv_score_kernel<DT><<<dim3(ntiles, B * H), LV_THREADS, 0, st>>>((const T*)k, k_sb, k_sh, k_ss, (const T*)phi,
-                                                                                                   p_sb, p_sh, p_sd, H, S, D, ks, L.nb,
-                                                                                                   mpart, minv, raw));
+               lv_score_kernel<DT><<<dim3(ntiles, B * H), LV_THREADS, 0, st>>>((const T*)k.p, k.sb, k.sh, k.ss, (const T*)p.p, p.sb, p.sh, p.ss, H, S, D, ks, w.nb,
+                                                                                w.mpart, w.minv, raw));
 }
 
 }  // namespace
@@ -767,13 +784,14 @@ void lv_run(const LvLayout& L, char* ws, hipStream_t st, const void* k, int64_t 
 // ================================================================================================================================
 extern "C" size_t kvp_ncattn_workspace_bytes(int64_t B, int64_t Hkv, int64_t S) {
     if (B < 1 || Hkv < 1 || S < 1) return 0;
-    return nc_ws_bytes(B, Hkv, S);
+    return nc_ws(nullptr, B, Hkv, S).total;
 }
 
 extern "C" int kvp_ncattn_score(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const void* cos, const void* sin, int64_t cs_sb,
                                 int64_t cs_ss, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* v, int64_t v_sb,
                                 int64_t v_sh, int64_t v_ss, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t D,
                                 int64_t chunk, float* raw, float* scores, void* ws, size_t ws_bytes, kvp_stream_t stream) {
+    NcCall c{{q, q_sb, q_sh, q_ss}, {k, k_sb, k_sh, k_ss}, {v, v_sb, v_sh, v_ss}, {cos, sin, cs_sb, cs_ss}};
     KVP_CHECK_ARG(q && cos && sin && k && v && scores && ws, "kvp_ncattn_score: null pointer");
     KVP_CHECK_DTYPE("kvp_ncattn_score", dtype);
     KVP_CHECK_ARG(chunk >= 1, "kvp_ncattn_score: chunk_size must be positive (got %lld)", (long long)chunk);
@@ -782,26 +800,23 @@ extern "C" int kvp_ncattn_score(const void* q, int64_t q_sb, int64_t q_sh, int64
     KVP_CHECK_ARG(S >= 1 && S < (1LL << 31) && D >= 2 && D % 2 == 0 && D <= 4096, "kvp_ncattn_score: bad shape (S=%lld D=%lld)", (long long)S,
                   (long long)D);
     KVP_CHECK_ARG(chunk <= (1LL << 30) && Hkv <= 65535 && B <= 65535, "kvp_ncattn_score: bad shape");
-    KVP_CHECK_ARG(ws_bytes >= nc_ws_bytes(B, Hkv, S), "kvp_ncattn_score: workspace too small (%zu < %zu)", ws_bytes, nc_ws_bytes(B, Hkv, S));
+    const NcWs w = nc_ws(ws, B, Hkv, S);
+    KVP_CHECK_ARG(ws_bytes >= w.total, "kvp_ncattn_score: workspace too small (%zu < %zu)", ws_bytes, w.total);
     hipStream_t st = (hipStream_t)stream;
-    const int64_t G = Hq / Hkv;
     const int64_t nchunks = (S + chunk - 1) / chunk;
     KVP_CHECK_ARG(nchunks <= 0x7fffffff, "kvp_ncattn_score: bad shape");
-    const size_t plane = kvp_align_up((size_t)(B * Hkv * S) * sizeof(float), 256);
-    float* tmp = (float*)ws;
-    float* rawp = raw ? raw : (float*)((char*)ws + plane);
-    ZsWs zw{(double*)((char*)ws + 2 * plane), (double*)((char*)ws + 2 * plane) + ZS_BLOCKS};
-    const bool mfma = nc_mfma_ok(dtype, D, chunk, G, k, k_sb, k_sh, k_ss, q_sh, q_ss, cs_ss, v_ss);
+    c.Hkv = (int)Hkv; c.G = (int)(Hq / Hkv); c.S = (int)S; c.C = (int)chunk; c.D = (int)D; c.tmp = w.tmp;
+    const bool mfma = nc_mfma_ok(c, dtype);
     const dim3 grid((unsigned)nchunks, (unsigned)Hkv, (unsigned)B);
     int rc;
-    KVP_DISPATCH_DTYPE(dtype, rc = nc_run<DT>(mfma, grid, st, q, q_sb, q_sh, q_ss, cos, sin, cs_sb, cs_ss, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, (int)Hkv, (int)G, (int)S, (int)chunk, (int)D, tmp));   // (mfma is false for float32: nc_mfma_ok)
+    KVP_DISPATCH_DTYPE(dtype, rc = nc_run<DT>(c, mfma, grid, st));   // (mfma is false for float32: nc_mfma_ok)
     if (rc != KVP_OK) return rc;
-    return zscore_launch(tmp, rawp, B * Hkv * S, S, 1, scores, zw, st);
+    return zscore_launch(w.tmp, raw ? raw : w.raw, B * Hkv * S, S, 1, scores, w.zs, st);
 }
 
 extern "C" size_t kvp_leverage_workspace_bytes(int64_t B, int64_t H, int64_t S, int64_t D, int64_t sketch) {
     if (B < 1 || H < 1 || S < 1 || D < 1 || sketch < 1) return 0;
-    return lv_layout(B, H, S, D, sketch).total;
+    return lv_ws(nullptr, B, H, S, D, sketch).total;
 }
 
 extern "C" int kvp_leverage_score(const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* phi, int64_t p_sb, int64_t p_sh,
@@ -812,24 +827,22 @@ extern "C" int kvp_leverage_score(const void* k, int64_t k_sb, int64_t k_sh, int
     KVP_CHECK_ARG(sketch >= 1 && sketch <= 256, "kvp_leverage_score: sketch_dimension must be in [1, 256] (got %lld)", (long long)sketch);
     KVP_CHECK_ARG(B >= 1 && H >= 1 && B * H <= 65535 && S >= 1 && S < (1LL << 31) && D >= 1 && D <= 256,
                   "kvp_leverage_score: bad shape (B=%lld H=%lld S=%lld D=%lld; D <= 256)", (long long)B, (long long)H, (long long)S, (long long)D);
-    const LvLayout L = lv_layout(B, H, S, D, sketch);
-    KVP_CHECK_ARG(ws_bytes >= L.total, "kvp_leverage_score: workspace too small (%zu < %zu)", ws_bytes, L.total);
+    const LvWs w = lv_ws(ws, B, H, S, D, sketch);
+    KVP_CHECK_ARG(ws_bytes >= w.total, "kvp_leverage_score: workspace too small (%zu < %zu)", ws_bytes, w.total);
     hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)ws;
-    float* rawp = raw ? raw : (float*)(w + L.raw);
-    KVP_DISPATCH_DTYPE(dtype, lv_run<DT>(L, w, st, k, k_sb, k_sh, k_ss, phi, p_sb, p_sh, p_sd, (int)B, (int)H, (int)S, (int)D, (int)sketch, rawp));
+    float* rawp = raw ? raw : w.raw;
+    KVP_DISPATCH_DTYPE(dtype, lv_run<DT>(w, st, {k, k_sb, k_sh, k_ss}, {phi, p_sb, p_sh, p_sd}, (int)B, (int)H, (int)S, (int)D, (int)sketch, rawp));
     KVP_CHECK_LAUNCH("kvp_leverage_score");
-    ZsWs zw{(double*)(w + L.zs), (double*)(w + L.zs) + ZS_BLOCKS};
-    return zscore_launch(rawp, rawp, B * H * S, S, 0, scores, zw, st);
+    return zscore_launch(rawp, rawp, B * H * S, S, 0, scores, w.zs, st);
 }
 
 extern "C" int kvp_leverage_status(const void* ws, int64_t B, int64_t H, int64_t S, int64_t D, int64_t sketch, kvp_stream_t stream) {
     KVP_CHECK_ARG(ws, "kvp_leverage_status: null pointer");
     KVP_CHECK_ARG(B >= 1 && H >= 1 && B * H <= 65535 && sketch >= 1 && sketch <= 256, "kvp_leverage_status: bad shape");
-    const LvLayout L = lv_layout(B, H, S, D, sketch);
+    const LvWs w = lv_ws(const_cast<void*>(ws), B, H, S, D, sketch);
     std::vector<int> st((size_t)(B * H));
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemcpyAsync(st.data(), (const char*)ws + L.status, st.size() * sizeof(int), hipMemcpyDeviceToHost, s);
+    hipError_t e = hipMemcpyAsync(st.data(), w.status, st.size() * sizeof(int), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) {
         kvp_set_error("kvp_leverage_status: %s", hipGetErrorString(e));

@@ -35,23 +35,17 @@ struct CompressWs {
 
 CompressWs carve(void* ws, int64_t R, int64_t S_select, int64_t S, int64_t n_kept, size_t scorer_bytes) {
     CompressWs w;
-    size_t off = 0;
-    char* base = static_cast<char*>(ws);
-    auto take = [&](size_t bytes) {
-        void* p = base ? base + off : nullptr;
-        off += kvp_align_up(bytes, 256);
-        return p;
-    };
+    KvpArena ar(ws);
     // the select may run over S (unfused fallback) or S_select <= S columns: size for the larger chunk count
     w.topk_bytes = std::max(kvp_topk_workspace_bytes(R, S, n_kept), kvp_topk_workspace_bytes(R, S_select, n_kept));
-    w.topk = take(w.topk_bytes);
-    w.scores = (float*)take((size_t)R * S * 4);
-    w.idx = (int32_t*)take((size_t)std::max<int64_t>(1, R * n_kept) * 4);
+    w.topk = ar.take<char>(w.topk_bytes);
+    w.scores = ar.take<float>((size_t)R * S);
+    w.idx = ar.take<int32_t>((size_t)std::max<int64_t>(1, R * n_kept));
     w.scorer_bytes = scorer_bytes;
-    w.scorer = take(scorer_bytes);
+    w.scorer = ar.take<char>(scorer_bytes);
     w.order_bytes = topk_order_workspace_bytes(R, n_kept);
-    w.order = take(w.order_bytes);
-    w.total_bytes = off;
+    w.order = ar.take<char>(w.order_bytes);
+    w.total_bytes = ar.bytes();
     return w;
 }
 
@@ -74,7 +68,7 @@ struct GatherKv {
     hipStream_t stream;
 };
 int gather(const GatherKv& g, const int32_t* idx) {
-    return kvp_gather_kv(g.k.p, g.k.sb, g.k.sh, g.k.ss, g.v.p, g.v.sb, g.v.sh, g.v.ss, g.dtype, g.B, g.H, g.S, g.D, idx, g.n_kept, g.k_out, g.v_out, g.stream);
+    return kvp_gather_launch(g.k, g.v, g.dtype, g.B, g.H, g.S, g.D, idx, g.n_kept, g.k_out, g.v_out, g.stream);
 }
 
 }  // namespace
@@ -100,10 +94,9 @@ extern "C" int kvp_knorm_compress(const void* k, int64_t k_sb, int64_t k_sh, int
     // long rows of 256-byte keys (Llama: D = 128, bf16 / f16): norms, select digits and compaction in ONE launch, the scores stay
     // in registers (topk_cluster.hip); other shapes / a device that cannot hold the grid / KVP_TK_CLUSTER=0: the sequence below
     const bool by_score = (flags & KVP_ORDER_SCORE) != 0;   // K' / V' rows in descending-score order (the reference's layout, scorer_press.py:95-100)
-    if (!by_score && n_kept < S && topk_cluster_eligible(R, S) && (dtype == KVP_BF16 || dtype == KVP_F16) && D == 128 && ((uintptr_t)k % 16) == 0 &&
-        (k_sb * 2) % 16 == 0 && (k_sh * 2) % 16 == 0 && (k_ss * 2) % 16 == 0) {
+    if (!by_score && n_kept < S && topk_cluster_eligible(R, S) && (dtype == KVP_BF16 || dtype == KVP_F16) && D == 128 && g.k.aligned(16, 2)) {
         TopkWs tw = topk_carve_ws(w.topk, R, (S + TK_CHUNK - 1) / TK_CHUNK);
-        const int rc = topk_cluster_select(TOPK_CLUSTER_KNORM, nullptr, 0, 1.f, k, dtype, k_sb, k_sh, k_ss, H, -1.0f, R, S, n_kept, w.idx, n_kept, 0, 0, tw,
+        const int rc = topk_cluster_select(TOPK_CLUSTER_KNORM, nullptr, 0, 1.f, g.k, dtype, H, -1.0f, R, S, n_kept, w.idx, n_kept, 0, 0, tw,
                                            false, stream);
         if (rc < 0) return rc;
         if (rc == 0) return gather(g, w.idx);
@@ -139,7 +132,7 @@ static int snapkv_select_gather(const CompressWs& w, bool fused, const float* co
         if (n_kept - W == 0 || n_kept == S)   // only the window / everything is kept: no selection
             rc = topk_select_impl(colsum, R, S - W, S - W, n_kept - W, w.idx, n_kept, (uint32_t)(S - W), (uint32_t)W, w.topk, w.topk_bytes, true, false, stream);
         else
-            rc = topk_cluster_select(TOPK_CLUSTER_POOL5, colsum, S - W, inv, nullptr, 0, 0, 0, 0, 1, 0.f, R, S - W, n_kept - W, w.idx, n_kept, (uint32_t)(S - W),
+            rc = topk_cluster_select(TOPK_CLUSTER_POOL5, colsum, S - W, inv, KvpRows{}, 0, 1, 0.f, R, S - W, n_kept - W, w.idx, n_kept, (uint32_t)(S - W),
                                      (uint32_t)W, tw, false, stream);
         KVP_CHECK_ARG(rc != 1, "snapkv_compress: cluster select not launchable");   // (snapkv_cluster_pooled() asked the same question before the scorer ran)
     } else if (fused && colsum)  // short rows, kernel_size 5: pooling happens inside the select's loader

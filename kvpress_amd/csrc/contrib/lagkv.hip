@@ -290,9 +290,7 @@ extern "C" int kvp_lagkv_score(const void* k, int64_t k_sb, int64_t k_sh, int64_
     KVP_LAUNCH("lagkv_ones_kernel", stream, lagkv_ones_kernel<<<dim3((uint32_t)std::min<int64_t>((S + 255) / 256, 1024), BH), 256, 0, stream>>>(scores, (uint32_t)S, (uint32_t)n_sink, scored_end));
     const dim3 grid(a.n_scored, BH);
     const size_t es = (size_t)kvp_elem_size(dtype), rowbytes = (size_t)D * es;
-    auto al16 = [&](int64_t st) { return ((size_t)st * es) % 16 == 0; };
-    const bool vec = rowbytes % 16 == 0 && rowbytes <= 1024 && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) && al16(k_sb) && al16(k_sh) && al16(k_ss) &&
-                     al16(v_sb) && al16(v_sh) && al16(v_ss);
+    const bool vec = rowbytes % 16 == 0 && rowbytes <= 1024 && KvpRows{k, k_sb, k_sh, k_ss}.aligned(16, es) && KvpRows{v, v_sb, v_sh, v_ss}.aligned(16, es);
     if (a.n_scored && vec) {
         const uint32_t chunks = (uint32_t)(rowbytes / 16);
         int lpr = 1;

@@ -151,8 +151,7 @@ extern "C" int kvp_think_channel_scores(const void* q, int64_t q_sb, int64_t q_s
     uint32_t nchunk = (uint32_t)((S + TH_ROWS - 1) / TH_ROWS);
     const uint32_t BH = (uint32_t)(B * Hkv);
     const size_t es = (size_t)kvp_elem_size(dtype), rowbytes = (size_t)D * es;
-    const bool vec = rowbytes % 16 == 0 && rowbytes <= 1024 && ((uintptr_t)k % 16 == 0) && (k_sb * es) % 16 == 0 && (k_sh * es) % 16 == 0 &&
-                     (k_ss * es) % 16 == 0;
+    const bool vec = rowbytes % 16 == 0 && rowbytes <= 1024 && KvpRows{k, k_sb, k_sh, k_ss}.aligned(16, es);
     if (vec) nchunk = std::max<uint32_t>(1, std::min<uint32_t>(nchunk, 2048 / std::max<uint32_t>(1, BH)));  // blocks striding over the rows
     uint32_t Dp = 1;
     while (Dp < (uint32_t)D) Dp <<= 1;   // power of two: TH_THREADS / Dp row phases

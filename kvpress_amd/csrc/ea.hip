@@ -334,22 +334,16 @@ struct EaScoreWs {
 
 EaScoreWs carve_score_ws(void* ws, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t D) {
     EaScoreWs w;
-    size_t off = 0;
-    char* base = static_cast<char*>(ws);
-    auto take = [&](size_t bytes) {
-        void* p = base ? base + off : nullptr;
-        off += kvp_align_up(bytes, 256);
-        return p;
-    };
+    KvpArena ar(ws);
     const size_t nblk = (size_t)(S + EA_SUB - 1) / EA_SUB;
-    w.bmax = (float*)take(2048 * 4);
-    w.logits = (float*)take((size_t)B * Hq * S * 4);
-    w.part_m = (float*)take((size_t)B * Hq * nblk * 4);
-    w.part_z = (float*)take((size_t)B * Hq * nblk * 4);
-    w.rowstat = (float*)take((size_t)B * Hq * 4);
-    w.vnorm = (float*)take((size_t)B * Hkv * S * 4);
-    w.scratch = take(ea_mfma_logits_scratch_bytes(B, Hq, D) + 256);
-    w.total_bytes = off;
+    w.bmax = ar.take<float>(2048);
+    w.logits = ar.take<float>((size_t)B * Hq * S);
+    w.part_m = ar.take<float>((size_t)B * Hq * nblk);
+    w.part_z = ar.take<float>((size_t)B * Hq * nblk);
+    w.rowstat = ar.take<float>((size_t)B * Hq);
+    w.vnorm = ar.take<float>((size_t)B * Hkv * S);
+    w.scratch = ar.take<char>(ea_mfma_logits_scratch_bytes(B, Hq, D) + 256);
+    w.total_bytes = ar.bytes();
     return w;
 }
 
@@ -362,13 +356,7 @@ struct EaStatWs {
 
 EaStatWs carve_stat_ws(void* ws, int64_t B, int64_t Hq, int64_t Sq, int64_t D) {
     EaStatWs w;
-    size_t off = 0;
-    char* base = static_cast<char*>(ws);
-    auto take = [&](size_t bytes) {
-        void* p = base ? base + off : nullptr;
-        off += kvp_align_up(bytes, 256);
-        return p;
-    };
+    KvpArena ar(ws);
     auto pick = [&](int64_t max_chunks, uint32_t& rows, uint32_t& nchunk) {
         int64_t r = std::max<int64_t>(256, (Sq + max_chunks - 1) / max_chunks);
         r = (r + 31) / 32 * 32;
@@ -377,9 +365,9 @@ EaStatWs carve_stat_ws(void* ws, int64_t B, int64_t Hq, int64_t Sq, int64_t D) {
     };
     pick(64, w.rows_mean, w.nchunk_mean);
     pick(16, w.rows_cov, w.nchunk_cov);
-    w.psum = (float*)take((size_t)B * Hq * w.nchunk_mean * D * 4);
-    w.pcov = (float*)take((size_t)B * Hq * w.nchunk_cov * D * D * 4);
-    w.total_bytes = off;
+    w.psum = ar.take<float>((size_t)B * Hq * w.nchunk_mean * D);
+    w.pcov = ar.take<float>((size_t)B * Hq * w.nchunk_cov * D * D);
+    w.total_bytes = ar.bytes();
     return w;
 }
 
@@ -394,6 +382,7 @@ extern "C" size_t kvp_ea_qstats_workspace_bytes(int64_t B, int64_t Hq, int64_t S
 extern "C" int kvp_ea_qstats(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, int dtype, int64_t B, int64_t Hq,
                              int64_t Sq, int64_t D, float* mu, float* cov, void* ws, size_t ws_bytes, kvp_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const KvpRows qv{q, q_sb, q_sh, q_ss};
     KVP_CHECK_DTYPE("ea_qstats", dtype);
     KVP_CHECK_ARG(B >= 1 && Hq >= 1 && Sq >= 1 && D >= 1 && D <= 1024, "ea_qstats: bad shape B=%ld Hq=%ld Sq=%ld D=%ld",
                   (long)B, (long)Hq, (long)Sq, (long)D);
@@ -401,8 +390,7 @@ extern "C" int kvp_ea_qstats(const void* q, int64_t q_sb, int64_t q_sh, int64_t 
     KVP_CHECK_ARG(q && mu, "ea_qstats: null pointer");
     const size_t need = kvp_ea_qstats_workspace_bytes(B, Hq, Sq, D);
     if (int rc = kvp_check_workspace("ea_qstats", ws, ws_bytes, need)) return rc;
-    if (ea_mfma_qstats_eligible(q, q_sb, q_sh, q_ss, dtype, Hq, Sq, D))
-        return ea_mfma_qstats(q, q_sb, q_sh, q_ss, dtype, B, Hq, Sq, D, mu, cov, ws, stream);
+    if (ea_mfma_qstats_eligible(qv, dtype, Hq, Sq, D)) return ea_mfma_qstats(qv, dtype, B, Hq, Sq, D, mu, cov, ws, stream);
 
     EaStatWs w = carve_stat_ws(ws, B, Hq, Sq, D);
     const float inv_n = (float)(1.0 / (double)Sq);
@@ -437,6 +425,8 @@ extern "C" int kvp_ea_score(const void* k, int64_t k_sb, int64_t k_sh, int64_t k
                             int64_t S, int64_t D, int64_t n_sink, int use_vnorm, float epsilon, float* scores, void* ws,
                             size_t ws_bytes, kvp_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const int64_t es = kvp_elem_size(dtype);
+    const KvpRows vv{v, v_sb, v_sh, v_ss};
     KVP_CHECK_DTYPE("ea_score", dtype);
     KVP_CHECK_ARG(B >= 1 && Hq >= 1 && Hkv >= 1 && Hq % Hkv == 0 && D >= 1 && D <= 1024, "ea_score: bad shape");
     KVP_CHECK_ARG(n_sink >= 0 && S > n_sink, "ea_score: Input should contain more tokens than n_sink=%ld", (long)n_sink);
@@ -464,19 +454,14 @@ extern "C" int kvp_ea_score(const void* k, int64_t k_sb, int64_t k_sh, int64_t k
         KVP_CHECK_ARG(lds <= 160 * 1024, "ea_score: D=%ld exceeds the generic kernel's LDS budget", (long)D);
         if (lds > 64 * 1024) {   // head sizes of 256 and more (Gemma: 66 KiB for the 64-key tile of float32 rows): above the default limit of a launch, inside the CU's 160 KiB -- was refused until round 6
             const void* fn = dtype == KVP_F32 ? (const void*)ea_logits_generic<KVP_F32> : dtype == KVP_F16 ? (const void*)ea_logits_generic<KVP_F16> : (const void*)ea_logits_generic<KVP_BF16>;
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-                kvp_set_error("ea_score: cannot raise the dynamic LDS limit to %zu bytes (D=%ld)", lds, (long)D);
-                return KVP_EHIP;
-            }
+            if (int rc = kvp_raise_dynamic_lds("ea_score", fn, lds)) return rc;
         }
         const dim3 grid(nblk, (uint32_t)Hq, (uint32_t)B);
         KVP_DISPATCH_DTYPE(dtype, KVP_LAUNCH("ea_logits_generic", stream, ea_logits_generic<DT><<<grid, EA_THREADS, lds, stream>>>(a, w.logits, nblk, w.part_m, w.part_z)));
     }
     const uint32_t nrows = (uint32_t)(B * Hq);
-    const int64_t es = kvp_elem_size(dtype);
-    auto al16 = [&](int64_t elems) { return (elems * es) % 16 == 0; };
-    if (use_vnorm && dtype != KVP_F32 && D * es == 256 && (Hq / Hkv == 1 || Hq / Hkv == 2 || Hq / Hkv == 4 || Hq / Hkv == 8 || Hq / Hkv == 16) && Sp >= 4096 && B * Hkv <= 1024 && ((uintptr_t)v % 16) == 0 && al16(v_sb) &&
-        al16(v_sh) && al16(v_ss) && kvp_env_int("KVP_EA_FUSED_FINALIZE", 1) != 0) {
+    if (use_vnorm && dtype != KVP_F32 && D * es == 256 && (Hq / Hkv == 1 || Hq / Hkv == 2 || Hq / Hkv == 4 || Hq / Hkv == 8 || Hq / Hkv == 16) && Sp >= 4096 && B * Hkv <= 1024 && vv.aligned(16, es) &&
+        kvp_env_int("KVP_EA_FUSED_FINALIZE", 1) != 0) {
         const uint32_t BH = (uint32_t)(B * Hkv);
         const uint64_t want = std::max<uint64_t>(1, (256 + BH - 1) / BH);   // about one 1024-thread workgroup per CU
         uint64_t rows = ((uint64_t)Sp + want - 1) / want;
@@ -484,8 +469,8 @@ extern "C" int kvp_ea_score(const void* k, int64_t k_sb, int64_t k_sh, int64_t k
         const uint32_t nslot = (uint32_t)(((uint64_t)Sp + rows - 1) / rows);
         const dim3 grid(nslot, BH);
         const bool nt = (uint64_t)BH * Sp * 256 > (192ull << 20);   // read-once V (rownorm.hip: rn_streaming)
-        const char* vp = static_cast<const char*>(v) + n_sink * v_ss * es;
-#define KVP_EVF(DTV, TT, NTV, GV) KVP_LAUNCH("ea_vnorm_finalize_kernel", stream, (ea_vnorm_finalize_kernel<DTV, NTV, GV><<<grid, EVF_THREADS, 0, stream>>>(reinterpret_cast<const TT*>(vp), v_sb, v_sh, v_ss, w.logits, w.part_m, w.part_z, nblk, (uint32_t)Hq, (uint32_t)Hkv, (uint32_t)S, (uint32_t)n_sink, epsilon, scores, w.bmax, (uint32_t)rows, a.clear_word)))
+        const KvpRows vp = vv.from_row(n_sink, es);
+#define KVP_EVF(DTV, TT, NTV, GV) KVP_LAUNCH("ea_vnorm_finalize_kernel", stream, (ea_vnorm_finalize_kernel<DTV, NTV, GV><<<grid, EVF_THREADS, 0, stream>>>(static_cast<const TT*>(vp.p), vp.sb, vp.sh, vp.ss, w.logits, w.part_m, w.part_z, nblk, (uint32_t)Hq, (uint32_t)Hkv, (uint32_t)S, (uint32_t)n_sink, epsilon, scores, w.bmax, (uint32_t)rows, a.clear_word)))
 #define KVP_EVF_G(DTV, TT, NTV) do { switch (Hq / Hkv) { case 1: KVP_EVF(DTV, TT, NTV, 1); break; case 2: KVP_EVF(DTV, TT, NTV, 2); break; case 4: KVP_EVF(DTV, TT, NTV, 4); break; case 8: KVP_EVF(DTV, TT, NTV, 8); break; default: KVP_EVF(DTV, TT, NTV, 16); break; } } while (0)
         if (dtype == KVP_BF16) { if (nt) KVP_EVF_G(KVP_BF16, uint16_t, true); else KVP_EVF_G(KVP_BF16, uint16_t, false); }
         else { if (nt) KVP_EVF_G(KVP_F16, _Float16, true); else KVP_EVF_G(KVP_F16, _Float16, false); }
@@ -496,10 +481,8 @@ extern "C" int kvp_ea_score(const void* k, int64_t k_sb, int64_t k_sh, int64_t k
     }
     KVP_LAUNCH("softmax_combine_kernel", stream, softmax_combine_kernel<<<(nrows + 3) / 4, 256, 0, stream>>>(w.part_m, w.part_z, nrows, nblk, w.rowstat));
     KVP_CHECK_LAUNCH("ea_score(logits)");
-    if (use_vnorm) {
-        const char* vp = static_cast<const char*>(v) + n_sink * v_ss * kvp_elem_size(dtype);
-        if (int rc = kvp_rownorm_launch_read_once({vp, v_sb, v_sh, v_ss}, dtype, B, Hkv, Sp, D, 1.0f, w.vnorm, stream)) return rc;
-    }
+    if (use_vnorm)
+        if (int rc = kvp_rownorm_launch_read_once(vv.from_row(n_sink, es), dtype, B, Hkv, Sp, D, 1.0f, w.vnorm, stream)) return rc;
     const uint64_t total = (uint64_t)B * Hkv * Sp;
     const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((total + EA_THREADS - 1) / EA_THREADS, 2048));
     KVP_LAUNCH("ea_finalize_kernel", stream, ea_finalize_kernel<<<blocks, EA_THREADS, 0, stream>>>(w.logits, w.rowstat, w.vnorm, (uint32_t)B, (uint32_t)Hq, (uint32_t)Hkv,

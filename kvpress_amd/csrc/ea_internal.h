@@ -13,10 +13,9 @@ struct EaArgs {
 };
 
 // MFMA fast paths (bf16/f16; D = 128, the statistics also D = 64 with neighbouring heads, the logits also D = 64 / 96)
-bool ea_mfma_qstats_eligible(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, int dtype, int64_t Hq, int64_t Sq, int64_t D);
+bool ea_mfma_qstats_eligible(KvpRows q, int dtype, int64_t Hq, int64_t Sq, int64_t D);
 size_t ea_mfma_qstats_ws_bytes(int64_t B, int64_t Hq, int64_t Sq, int64_t D);
-int ea_mfma_qstats(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, int dtype, int64_t B, int64_t Hq, int64_t Sq,
-                   int64_t D, float* mu, float* cov, void* ws, hipStream_t stream);
+int ea_mfma_qstats(KvpRows q, int dtype, int64_t B, int64_t Hq, int64_t Sq, int64_t D, float* mu, float* cov, void* ws, hipStream_t stream);
 
 bool ea_mfma_logits_eligible(const EaArgs& a, int dtype);
 size_t ea_mfma_logits_scratch_bytes(int64_t B, int64_t Hq, int64_t D);

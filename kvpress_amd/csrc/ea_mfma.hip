@@ -1089,16 +1089,13 @@ __global__ __launch_bounds__(EB_THREADS, 1) void ea_logits_mfma_big_kernel(EaArg
 }
 constexpr size_t EB_LDS_BYTES = 2 * EB_TILEB + 2 * 4 * EL_TILE * 4 + 256 * 4 + 4 * 4;
 
-bool aligned8(int64_t x) { return x % 8 == 0; }
-
 }  // namespace
 
 // ---- host ---------------------------------------------------------------------------------------
-bool ea_mfma_qstats_eligible(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, int dtype, int64_t Hq, int64_t Sq, int64_t D) {
+bool ea_mfma_qstats_eligible(KvpRows q, int dtype, int64_t Hq, int64_t Sq, int64_t D) {
     // 16-bit rounding of the shifted products: relative covariance error ~ 4.6e-3 / sqrt(Sq) (1 sigma); shorter
     // sequences take the exact fp32 generic kernels
-    const bool ok = (dtype == KVP_BF16 || dtype == KVP_F16) && Sq >= 4096 && (uintptr_t)q % 16 == 0 && aligned8(q_sb) && aligned8(q_sh) && aligned8(q_ss);
-    (void)q_sh; (void)Hq;
+    const bool ok = (dtype == KVP_BF16 || dtype == KVP_F16) && Sq >= 4096 && q.aligned(16, 2);
     // Round 6, D = 64: the queries as the projection leaves them -- [B, S, Hq, 64] seen as [B, Hq, S, 64], heads 64 elements apart -- are rows
     // of Hq / 2 "heads" of 128 dimensions; the syrk of such a pair holds the two heads' second moments in its diagonal blocks (twice the matrix
     // work a 64-wide syrk needs, on a kernel that waits for HBM).  D = 96 and the other layouts of D = 64: a head of 128 dimensions whose upper
@@ -1120,13 +1117,12 @@ size_t ea_mfma_qstats_ws_bytes(int64_t B, int64_t Hq, int64_t Sq, int64_t D) {
     return need;
 }
 
-int ea_mfma_qstats(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, int dtype, int64_t B, int64_t Hq, int64_t Sq, int64_t D,
-                   float* mu, float* cov, void* ws, hipStream_t stream) {
-    const uint32_t pair = qstats_pairs(q_sh, Hq, D), quarters = D == 256;
-    if (pair) { Hq /= 2; q_sh = 128; }   // pairs of neighbouring 64-dimensional heads as heads of 128 (ea_mfma_qstats_eligible)
+int ea_mfma_qstats(KvpRows q, int dtype, int64_t B, int64_t Hq, int64_t Sq, int64_t D, float* mu, float* cov, void* ws, hipStream_t stream) {
+    const uint32_t pair = qstats_pairs(q.sh, Hq, D), quarters = D == 256;
+    if (pair) { Hq /= 2; q.sh = 128; }   // pairs of neighbouring 64-dimensional heads as heads of 128 (ea_mfma_qstats_eligible)
     if (quarters) Hq *= 6;               // D = 256: six pairs of quarters per head (QstatArgs::quarters)
     QstatArgs a;
-    a.q = q; a.q_sb = q_sb; a.q_sh = q_sh; a.q_ss = q_ss;
+    a.q = q.p; a.q_sb = q.sb; a.q_sh = q.sh; a.q_ss = q.ss;
     a.B = (uint32_t)B; a.Hq = (uint32_t)Hq; a.Sq = (uint32_t)Sq;
     qstats_plan(Sq, B * Hq, a.nchunk, a.rows_per_chunk);
     a.nch = (pair || quarters) ? 16u : (uint32_t)(D / 8);
@@ -1147,8 +1143,8 @@ int ea_mfma_qstats(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, int 
 }
 
 bool ea_mfma_logits_eligible(const EaArgs& a, int dtype) {
-    return (dtype == KVP_BF16 || dtype == KVP_F16) && (a.D == 128 || a.D == 64 || a.D == 96 || a.D == 256) && a.Sp >= 64 && (uintptr_t)a.k % 16 == 0 && aligned8(a.k_sb) &&
-           aligned8(a.k_sh) && aligned8(a.k_ss) && a.G <= 65535;
+    return (dtype == KVP_BF16 || dtype == KVP_F16) && (a.D == 128 || a.D == 64 || a.D == 96 || a.D == 256) && a.Sp >= 64 &&
+           KvpRows{a.k, a.k_sb, a.k_sh, a.k_ss}.aligned(16, 2) && a.G <= 65535;
 }
 size_t ea_mfma_logits_scratch_bytes(int64_t, int64_t, int64_t) { return 0; }
 // Keys per workgroup: 4096, doubled while the grid exceeds ONE resident round (two 4-wave workgroups per CU).  A workgroup's start-up
@@ -1190,10 +1186,7 @@ int ea_mfma_logits(const EaArgs& a, int dtype, float* logits, uint32_t nblk, flo
         const void* fns[4] = {(const void*)ea_logits_mfma_big_kernel<KVP_BF16, true>, (const void*)ea_logits_mfma_big_kernel<KVP_BF16, false>,
                               (const void*)ea_logits_mfma_big_kernel<KVP_F16, true>, (const void*)ea_logits_mfma_big_kernel<KVP_F16, false>};
         const void* fn = fns[(dtype == KVP_BF16 ? 0 : 2) + (a.cov ? 0 : 1)];
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EB_LDS_BYTES) != hipSuccess) {
-            kvp_set_error("ea_logits_mfma: cannot raise the dynamic LDS limit to %zu bytes", EB_LDS_BYTES);
-            return KVP_EHIP;
-        }
+        if (int rc = kvp_raise_dynamic_lds("ea_logits_mfma", fn, EB_LDS_BYTES)) return rc;
         if (dtype == KVP_BF16) {
             if (a.cov) KVP_LAUNCH("ea_logits_mfma", stream, (ea_logits_mfma_big_kernel<KVP_BF16, true><<<grid, EB_THREADS, EB_LDS_BYTES, stream>>>(a, logits, nblk, ck, part_m, part_z)));
             else KVP_LAUNCH("ea_logits_mfma", stream, (ea_logits_mfma_big_kernel<KVP_BF16, false><<<grid, EB_THREADS, EB_LDS_BYTES, stream>>>(a, logits, nblk, ck, part_m, part_z)));

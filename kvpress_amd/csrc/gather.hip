@@ -113,10 +113,8 @@ __global__ __launch_bounds__(GA_THREADS) void gather_scalar_kernel(GatherArgs a,
 
 }  // namespace
 
-extern "C" int kvp_gather_kv(const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* v, int64_t v_sb,
-                             int64_t v_sh, int64_t v_ss, int dtype, int64_t B, int64_t H, int64_t S, int64_t D,
-                             const int32_t* idx, int64_t n, void* k_out, void* v_out, kvp_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+int kvp_gather_launch(KvpRows k, KvpRows v, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, const int32_t* idx, int64_t n, void* k_out,
+                      void* v_out, hipStream_t stream) {
     if (int rc = kvp_async_check("kvp_gather_kv")) return rc;
     KVP_CHECK_DTYPE("gather", dtype);
     KVP_CHECK_ARG(B >= 0 && H >= 0 && S >= 0 && D >= 1 && n >= 0 && n <= S, "gather: bad shape B=%ld H=%ld S=%ld D=%ld n=%ld",
@@ -124,21 +122,18 @@ extern "C" int kvp_gather_kv(const void* k, int64_t k_sb, int64_t k_sh, int64_t 
     const int64_t nrows64 = B * H * n;
     if (nrows64 == 0) return KVP_OK;
     KVP_CHECK_ARG(n * D < ((int64_t)1 << 31) && S < ((int64_t)1 << 31) && B * H <= 65535, "gather: shape too large");
-    KVP_CHECK_ARG(k && v && idx && k_out && v_out, "gather: null pointer");
+    KVP_CHECK_ARG(k.p && v.p && idx && k_out && v_out, "gather: null pointer");
     const int64_t es = kvp_elem_size(dtype);
     GatherArgs a;
-    a.k = static_cast<const char*>(k); a.v = static_cast<const char*>(v);
+    a.k = static_cast<const char*>(k.p); a.v = static_cast<const char*>(v.p);
     a.ko = static_cast<char*>(k_out); a.vo = static_cast<char*>(v_out);
     a.idx = idx;
-    a.k_sb = k_sb * es; a.k_sh = k_sh * es; a.k_ss = k_ss * es;
-    a.v_sb = v_sb * es; a.v_sh = v_sh * es; a.v_ss = v_ss * es;
+    a.k_sb = k.sb * es; a.k_sh = k.sh * es; a.k_ss = k.ss * es;
+    a.v_sb = v.sb * es; a.v_sh = v.sh * es; a.v_ss = v.ss * es;
     a.H = (uint32_t)H; a.S = (uint32_t)S; a.n = (uint32_t)n;
     a.rowbytes = (uint32_t)(D * es);
     const uint32_t BH = (uint32_t)(B * H);
-    auto al16 = [](int64_t x) { return x % 16 == 0; };
-    const bool vec_ok = a.rowbytes % 16 == 0 && al16((int64_t)(uintptr_t)k) && al16((int64_t)(uintptr_t)v) &&
-                        al16((int64_t)(uintptr_t)k_out) && al16((int64_t)(uintptr_t)v_out) && al16(a.k_sb) &&
-                        al16(a.k_sh) && al16(a.k_ss) && al16(a.v_sb) && al16(a.v_sh) && al16(a.v_ss);
+    const bool vec_ok = a.rowbytes % 16 == 0 && k.aligned(16, es) && v.aligned(16, es) && (((uintptr_t)k_out | (uintptr_t)v_out) % 16) == 0;
     if (!vec_ok) {
         const uint64_t total = (uint64_t)n * (uint64_t)D;
         const uint32_t bx = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((total + GA_THREADS - 1) / GA_THREADS, 1024));
@@ -174,4 +169,10 @@ extern "C" int kvp_gather_kv(const void* k, int64_t k_sb, int64_t k_sh, int64_t 
 #undef KVP_GA_CASE
     KVP_CHECK_LAUNCH("gather");
     return KVP_OK;
+}
+
+extern "C" int kvp_gather_kv(const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* v, int64_t v_sb,
+                             int64_t v_sh, int64_t v_ss, int dtype, int64_t B, int64_t H, int64_t S, int64_t D,
+                             const int32_t* idx, int64_t n, void* k_out, void* v_out, kvp_stream_t stream_) {
+    return kvp_gather_launch({k, k_sb, k_sh, k_ss}, {v, v_sb, v_sh, v_ss}, dtype, B, H, S, D, idx, n, k_out, v_out, static_cast<hipStream_t>(stream_));
 }

@@ -238,8 +238,7 @@ KdPlan plan_for(const void* x, const KdMap& map, uint32_t BH, uint32_t D) {
     const size_t es = sizeof(typename Elem<DT>::T);
     const size_t rowbytes = (size_t)D * es;
     KdPlan p{};
-    p.vec = rowbytes % 16 == 0 && rowbytes <= 1024 && ((uintptr_t)x % 16 == 0) && (map.sb * es) % 16 == 0 &&
-            (map.sh * es) % 16 == 0 && (map.ss * es) % 16 == 0;
+    p.vec = rowbytes % 16 == 0 && rowbytes <= 1024 && KvpRows{x, map.sb, map.sh, map.ss}.aligned(16, es);
     if (p.vec) {
         p.chunks = (uint32_t)(rowbytes / 16);
         p.lpr = 1;

@@ -13,9 +13,6 @@
 
 #include "kvp_host.h"
 
-static inline size_t kvp_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-static inline int kvp_elem_size(int dtype) { return dtype == KVP_F32 ? 4 : 2; }
-
 // ---- element access ---------------------------------------------------------------------------
 template <int DT> struct Elem;
 template <> struct Elem<KVP_F32> {

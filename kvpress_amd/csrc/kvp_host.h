@@ -1,6 +1,9 @@
-// Host side of libkvpress_hip.so that more than one .hip uses: error / launch plumbing, argument helpers and every launcher that one
-// .hip defines and another calls (the families with a header of their own keep theirs: snapkv_internal.h, ea_internal.h,
-// topk_internal.h).  Included by kvp_common.h.  The library is compiled with -fvisibility=hidden: the extern "C" entries of
+// Host side of libkvpress_hip.so that more than one .hip uses: error / launch plumbing, the host-side views of the C ABI's flat
+// arguments (KvpRows: a strided [B,H,S,D] tensor and its alignment test; KvpRope: the rotary tables), the workspace arena every
+// layout is carved with (KvpArena), kvp_raise_dynamic_lds, and every launcher that one .hip defines and another calls (the families
+// with a header of their own keep theirs: snapkv_internal.h, ea_internal.h, topk_internal.h).  An extern "C" entry builds its views
+// once from its flat arguments; the flat lists come back only in a kernel launch expression.  Included by kvp_common.h.
+// The library is compiled with -fvisibility=hidden: the extern "C" entries of
 // include/*.h are exported (kvp_common.h), the KVP_INTERNAL_API functions below for csrc/contrib/*.hip, nothing else.
 #pragma once
 
@@ -70,11 +73,56 @@ KVP_INTERNAL_API void kvp_prof_end(hipStream_t stream);
 // tuning knobs read from the environment once (KVP_* variables; used for A/B runs on hardware)
 int kvp_env_int(const char* name, int dflt);
 
+static inline size_t kvp_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+static inline int kvp_elem_size(int dtype) { return dtype == KVP_F32 ? 4 : 2; }
+
 // a [B, H, S, D] tensor as the C ABI passes it: base pointer + element strides of the three outer dims (rows contiguous)
 struct KvpRows {
     const void* p;
     int64_t sb, sh, ss;
+    // are the base pointer and the three strides multiples of `bytes` (a power of two), for elements of `es` bytes?
+    bool aligned(size_t bytes, size_t es) const { return (((uintptr_t)p | (uintptr_t)sb * es | (uintptr_t)sh * es | (uintptr_t)ss * es) & (bytes - 1)) == 0; }
+    // the view from row s on
+    KvpRows from_row(int64_t s, size_t es) const { return {static_cast<const char*>(p) + s * ss * (int64_t)es, sb, sh, ss}; }
 };
+// the rotary tables cos, sin [1 or B, W, D]: element strides of the two outer dims
+struct KvpRope {
+    const void *cosp, *sinp;
+    int64_t sb, sw;
+    bool aligned(size_t bytes, size_t es) const { return (((uintptr_t)cosp | (uintptr_t)sinp | (uintptr_t)sb * es | (uintptr_t)sw * es) & (bytes - 1)) == 0; }
+};
+
+// the hidden states of the window [B, W, hidden] (element strides sb, sw) + q_proj.weight
+struct KvpHidden {
+    const void* p;
+    int64_t sb, sw;
+    const void* wq;
+    int64_t hidden;
+    // the two base pointers and the two strides of the hidden states
+    bool aligned(size_t bytes, size_t es) const { return (((uintptr_t)p | (uintptr_t)wq | (uintptr_t)sb * es | (uintptr_t)sw * es) & (bytes - 1)) == 0; }
+};
+
+// One workspace layout = one sequence of take()s over the caller's buffer; every region starts on a multiple of 256 bytes.  A null
+// base serves the size queries (the pointers are then null, bytes() is the same).  (topk_internal.h's TopkWsLayout stays word-based:
+// it is __host__ __device__ and the cluster kernel derives addresses from it.)
+struct KvpArena {
+    char* base;
+    size_t off = 0;
+    explicit KvpArena(void* ws) : base(static_cast<char*>(ws)) {}
+    template <class T> T* take(size_t count) {
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += kvp_align_up(count * sizeof(T), 256);
+        return p;
+    }
+    size_t bytes() const { return off; }
+};
+
+// raise a kernel's dynamic LDS limit to `bytes` (above the 64 KiB a launch gets by default): KVP_OK, or KVP_EHIP with the message set
+template <class Kernel> int kvp_raise_dynamic_lds(const char* who, Kernel* fn, size_t bytes) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) return KVP_OK;
+    kvp_set_error("%s: cannot raise the dynamic LDS limit to %zu bytes", who, bytes);
+    return KVP_EHIP;
+}
 
 // ---- launchers shared between files ------------------------------------------------------------------------------------------
 // rownorm.hip: out[b,h,s] = scale * ||x[b,h,s,:]||.  hist1 (may be null): also accumulate the select's first histogram; *hist1_done says
@@ -84,8 +132,9 @@ int kvp_rownorm_launch(KvpRows x, int dtype, int64_t B, int64_t H, int64_t S, in
 int kvp_rownorm_launch_read_once(KvpRows x, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, float scale, float* out, hipStream_t stream);
 int kvp_rowsumsq2_launch(KvpRows k, KvpRows v, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, float* out_k, float* out_v,
                          hipStream_t stream);
-// qproj.hip: RoPE'd window queries [B,Hq,W,D] from the hidden states x [B,W,K] (strides x_sb, x_sw) and q_proj's weight w
-bool kvp_qproj_rope_eligible(int dtype, int64_t W, int64_t D, int64_t K, const void* x, int64_t x_sb, int64_t x_sw, const void* w,
-                             const void* cosp, const void* sinp, int64_t cs_sb, int64_t cs_sw);
-int kvp_qproj_rope_launch(const void* x, int64_t x_sb, int64_t x_sw, const void* w, const void* cosp, const void* sinp, int64_t cs_sb,
-                          int64_t cs_sw, int dtype, int64_t B, int64_t Hq, int64_t K, void* out, hipStream_t stream);
+// gather.hip: K, V [B,H,S,D] -> contiguous K', V' [B,H,n,D] at idx [B,H,n] (the body of kvp_gather_kv)
+int kvp_gather_launch(KvpRows k, KvpRows v, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, const int32_t* idx, int64_t n, void* k_out,
+                      void* v_out, hipStream_t stream);
+// qproj.hip: RoPE'd window queries [B,Hq,W,D] from the hidden states and q_proj's weight
+bool kvp_qproj_rope_eligible(int dtype, int64_t W, int64_t D, const KvpHidden& x, const KvpRope& r);
+int kvp_qproj_rope_launch(const KvpHidden& x, const KvpRope& r, int dtype, int64_t B, int64_t Hq, void* out, hipStream_t stream);

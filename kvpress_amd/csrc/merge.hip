@@ -35,27 +35,36 @@ __device__ __forceinline__ void better(float& bv, int& bi, float v, int i) {
 }
 
 // ---- workspace layout (per row r = b * H + h; arrays of S entries per row) -----------------------------------------------------
-struct MrgLayout {
+struct MrgWs {
     int64_t ntile;
-    size_t ev, inv, vn, ms, tg, w, cnt, lst, tcnt, thr, total;
+    int32_t* ev;    // evicted positions, ascending
+    float* inv;     // 1 / max(||k||, eps): [0, n_kept) kept rows (K' order), [n_kept, S) evicted rows
+    float* vn;      // ||v||, same layout
+    float* ms;      // max_sim [n_evict]
+    int32_t* tg;    // target [n_evict]
+    float* w;       // weights [n_evict]; before them the argmax partial maxima (P * n_evict <= S)
+    int32_t* cnt;   // [S + 1] per row: the kept mask, then counts -> bucket ends per kept row
+    int32_t* lst;   // bucket contents; before them the argmax partial indices
+    int32_t* tcnt;  // [ntile]
+    float* thr;     // one per row
+    size_t total;
 };
-MrgLayout mrg_layout(int64_t R, int64_t S) {
-    MrgLayout L;
+MrgWs mrg_ws(void* ws, int64_t R, int64_t S) {
+    MrgWs L;
     L.ntile = (S + TILE - 1) / TILE;
-    size_t off = 0;
-    auto take = [&](size_t n) { const size_t o = off; off = kvp_align_up(off + n, 256); return o; };
-    const size_t row4 = (size_t)R * S * 4;
-    L.ev = take(row4);    // int32 evicted positions, ascending
-    L.inv = take(row4);   // float 1 / max(||k||, eps): [0, n_kept) kept rows (K' order), [n_kept, S) evicted rows
-    L.vn = take(row4);    // float ||v||, same layout
-    L.ms = take(row4);    // float max_sim [n_evict]
-    L.tg = take(row4);    // int32 target [n_evict]
-    L.w = take(row4);     // float weights [n_evict]; before them the argmax partial maxima (P * n_evict <= S)
-    L.cnt = take((size_t)R * (S + 1) * 4);   // int32: the kept mask, then counts -> bucket ends per kept row
-    L.lst = take(row4);   // int32 bucket contents; before them the argmax partial indices
-    L.tcnt = take((size_t)R * L.ntile * 4);
-    L.thr = take((size_t)R * 4);
-    L.total = off;
+    KvpArena ar(ws);
+    const size_t row = (size_t)R * S;
+    L.ev = ar.take<int32_t>(row);
+    L.inv = ar.take<float>(row);
+    L.vn = ar.take<float>(row);
+    L.ms = ar.take<float>(row);
+    L.tg = ar.take<int32_t>(row);
+    L.w = ar.take<float>(row);
+    L.cnt = ar.take<int32_t>((size_t)R * (S + 1));
+    L.lst = ar.take<int32_t>(row);
+    L.tcnt = ar.take<int32_t>((size_t)R * L.ntile);
+    L.thr = ar.take<float>((size_t)R);
+    L.total = ar.bytes();
     return L;
 }
 
@@ -525,28 +534,18 @@ __global__ __launch_bounds__(MT) void mrg_merge_kernel(const typename Elem<DT>::
     }
 }
 
-bool mfma_ok(int dtype, int64_t D, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* ko) {
+bool mfma_ok(int dtype, int64_t D, KvpRows k, const void* ko) {
     if (dtype == KVP_F32 || !(D == 64 || D == 96 || D == 128 || D == 256)) return false;
-    if (((uintptr_t)k | (uintptr_t)ko) & 15) return false;
-    return (k_sb % 8 == 0) && (k_sh % 8 == 0) && (k_ss % 8 == 0);
+    return k.aligned(16, 2) && ((uintptr_t)ko % 16) == 0;
 }
 
 template <int DT>
-int mrg_run(const MrgLayout& L, char* ws, hipStream_t st, const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* v, int64_t v_sb,
-            int64_t v_sh, int64_t v_ss, const int32_t* kept, const void* ko, void* vo, int64_t B, int64_t H, int64_t S, int64_t nk, int64_t D,
-            float thr, float q, bool frac, int32_t* tg_out, float* ms_out) {
+int mrg_run(const MrgWs& L, hipStream_t st, KvpRows k, KvpRows v, const int32_t* kept, const void* ko, void* vo, int64_t B, int64_t H, int64_t S,
+            int64_t nk, int64_t D, float thr, float q, bool frac, int32_t* tg_out, float* ms_out) {
     using T = typename Elem<DT>::T;
     const int64_t R = B * H, ne = S - nk;
-    int32_t* ev = (int32_t*)(ws + L.ev);
-    float* inv = (float*)(ws + L.inv);
-    float* vn = (float*)(ws + L.vn);
-    float* ms = (float*)(ws + L.ms);
-    int32_t* tg = (int32_t*)(ws + L.tg);
-    float* w = (float*)(ws + L.w);
-    int32_t* cnt = (int32_t*)(ws + L.cnt);
-    int32_t* lst = (int32_t*)(ws + L.lst);
-    int32_t* tcnt = (int32_t*)(ws + L.tcnt);
-    float* qthr = (float*)(ws + L.thr);
+    int32_t *const ev = L.ev, *const tg = L.tg, *const cnt = L.cnt, *const lst = L.lst, *const tcnt = L.tcnt;
+    float *const inv = L.inv, *const vn = L.vn, *const ms = L.ms, *const w = L.w, *const qthr = L.thr;
     const size_t cnt_bytes = (size_t)R * (S + 1) * 4;
 
     // 1. prep
@@ -559,12 +558,12 @@ int mrg_run(const MrgLayout& L, char* ws, hipStream_t st, const void* k, int64_t
     KVP_LAUNCH("merge_compact", st, mrg_compact_kernel<<<dim3((unsigned)L.ntile, (unsigned)R), MT, 0, st>>>(cnt, S, L.ntile, tcnt, ne, ev));
     KVP_LAUNCH("merge_norms", st,
                mrg_norms_kernel<DT><<<dim3((unsigned)((S + MT / 64 - 1) / (MT / 64)), (unsigned)R), MT, 0, st>>>(
-                   (const T*)k, k_sb, k_sh, k_ss, (const T*)v, v_sb, v_sh, v_ss, (const T*)ko, (const T*)vo, (int)H, S, nk, (int)D, ev, inv, vn));
+                   (const T*)k.p, k.sb, k.sh, k.ss, (const T*)v.p, v.sb, v.sh, v.ss, (const T*)ko, (const T*)vo, (int)H, S, nk, (int)D, ev, inv, vn));
     KVP_CHECK_LAUNCH("merge prep");
 
     // 2. nearest survivor: split the kept rows when the evicted rows alone give fewer than ~2 workgroups per CU (P * ne <= S keeps
     // the partial maxima inside the weight / bucket arrays)
-    const bool mf = mfma_ok(DT, D, k, k_sb, k_sh, k_ss, ko);   // false for float32
+    const bool mf = mfma_ok(DT, D, k, ko);   // false for float32
     int evb = GN_EV, kgran = GN_KT;
     if (mf) {
         evb = D <= 128 ? AmGeo<128>::EVB : AmGeo<256>::EVB;
@@ -582,7 +581,7 @@ int mrg_run(const MrgLayout& L, char* ws, hipStream_t st, const void* k, int64_t
       if (mf) {
         switch (D) {
 #define MRG_AM(D_) \
-    case D_: KVP_LAUNCH("merge_argmax_mfma", st, mrg_argmax_mfma_kernel<DT, D_><<<ag, AM_WAVES * 64, 0, st>>>((const T*)k, k_sb, k_sh, k_ss, (const T*)ko, (int)H, S, nk, ne, kchunk, ev, inv, pval, pidx)); break;
+    case D_: KVP_LAUNCH("merge_argmax_mfma", st, mrg_argmax_mfma_kernel<DT, D_><<<ag, AM_WAVES * 64, 0, st>>>((const T*)k.p, k.sb, k.sh, k.ss, (const T*)ko, (int)H, S, nk, ne, kchunk, ev, inv, pval, pidx)); break;
             MRG_AM(64)
             MRG_AM(96)
             MRG_AM(128)
@@ -595,7 +594,7 @@ int mrg_run(const MrgLayout& L, char* ws, hipStream_t st, const void* k, int64_t
     if (!mf) {
         const size_t lds = (size_t)(GN_EV * (D + 1) + GN_KT * D + GN_KT) * sizeof(float);
         KVP_LAUNCH("merge_argmax_generic", st,
-                   mrg_argmax_generic_kernel<DT><<<ag, MT, lds, st>>>((const T*)k, k_sb, k_sh, k_ss, (const T*)ko, (int)H, S, nk, ne, (int)D, kchunk,
+                   mrg_argmax_generic_kernel<DT><<<ag, MT, lds, st>>>((const T*)k.p, k.sb, k.sh, k.ss, (const T*)ko, (int)H, S, nk, ne, (int)D, kchunk,
                                                                       ev, inv, pval, pidx));
         KVP_CHECK_LAUNCH("mrg_argmax_generic_kernel");
     }
@@ -614,7 +613,7 @@ int mrg_run(const MrgLayout& L, char* ws, hipStream_t st, const void* k, int64_t
     KVP_LAUNCH("merge_fill", st, mrg_fill_kernel<<<eg, MT, 0, st>>>(tg, w, S, ne, cnt, lst));
     KVP_LAUNCH("merge_values", st,
                mrg_merge_kernel<DT><<<dim3((unsigned)((nk + MT / 64 - 1) / (MT / 64)), (unsigned)R), MT, 0, st>>>(
-                   (const T*)v, v_sb, v_sh, v_ss, (T*)vo, (int)H, S, nk, ne, (int)D, ev, tg, w, cnt, lst));
+                   (const T*)v.p, v.sb, v.sh, v.ss, (T*)vo, (int)H, S, nk, ne, (int)D, ev, tg, w, cnt, lst));
     KVP_CHECK_LAUNCH("merge");
     return KVP_OK;
 }
@@ -625,7 +624,7 @@ int mrg_run(const MrgLayout& L, char* ws, hipStream_t st, const void* k, int64_t
 extern "C" size_t kvp_merge_workspace_bytes(int64_t B, int64_t H, int64_t S, int64_t n_kept, int64_t D) {
     (void)D;
     if (B < 1 || H < 1 || S < 1 || n_kept < 0 || n_kept > S) return 0;
-    return mrg_layout(B * H, S).total;
+    return mrg_ws(nullptr, B * H, S).total;
 }
 
 extern "C" int kvp_merge_values(const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, const void* v, int64_t v_sb, int64_t v_sh,
@@ -640,11 +639,11 @@ extern "C" int kvp_merge_values(const void* k, int64_t k_sb, int64_t k_sh, int64
     const int64_t ne = S - n_kept;
     if (ne == 0 || n_kept == 0) return KVP_OK;   // merging_press.py:120-121: nothing to merge
     KVP_CHECK_ARG(k && v && kept_idx && k_out && v_out && ws, "kvp_merge_values: null pointer");
-    const MrgLayout L = mrg_layout(B * H, S);
+    const MrgWs L = mrg_ws(ws, B * H, S);
     if (int rc = kvp_check_workspace("kvp_merge_values", ws, ws_bytes, L.total)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const float thr = (float)similarity_threshold;          // `max_sim >= threshold` compares in float32
     const float q = (float)(1.0 - merge_fraction);          // torch.quantile's q tensor has the input's dtype
     const bool frac = merge_fraction < 1.0;
-    KVP_DISPATCH_DTYPE(dtype, return mrg_run<DT>(L, (char*)ws, st, k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, kept_idx, k_out, v_out, B, H, S, n_kept, D, thr, q, frac, target, max_sim));
+    KVP_DISPATCH_DTYPE(dtype, return mrg_run<DT>(L, st, {k, k_sb, k_sh, k_ss}, {v, v_sb, v_sh, v_ss}, kept_idx, k_out, v_out, B, H, S, n_kept, D, thr, q, frac, target, max_sim));
 }

@@ -157,23 +157,21 @@ __global__ __launch_bounds__(QP_THREADS) void qproj_rope_kernel(QprojArgs a) {
 
 }  // namespace
 
-bool kvp_qproj_rope_eligible(int dtype, int64_t W, int64_t D, int64_t K, const void* x, int64_t x_sb, int64_t x_sw, const void* w,
-                             const void* cosp, const void* sinp, int64_t cs_sb, int64_t cs_sw) {
+bool kvp_qproj_rope_eligible(int dtype, int64_t W, int64_t D, const KvpHidden& x, const KvpRope& r) {
+    const int64_t K = x.hidden;
     if (dtype != KVP_BF16 && dtype != KVP_F16) return false;
     if (W != QP_ROWS || D != 128 || K < QP_KT || K % QP_KT != 0) return false;
-    auto al8 = [](int64_t v) { return v % 8 == 0; };
-    if (((uintptr_t)x % 16) || ((uintptr_t)w % 16) || ((uintptr_t)cosp % 2) || ((uintptr_t)sinp % 2)) return false;
-    return al8(x_sb) && al8(x_sw) && cs_sb >= 0 && cs_sw >= 0;
+    if (!x.aligned(16, 2) || ((uintptr_t)r.cosp % 2) || ((uintptr_t)r.sinp % 2)) return false;
+    return r.sb >= 0 && r.sw >= 0;
 }
 
 // out: [B, Hq, 64, 128] contiguous in the input dtype.  Strides in elements.
-int kvp_qproj_rope_launch(const void* x, int64_t x_sb, int64_t x_sw, const void* w, const void* cosp, const void* sinp, int64_t cs_sb,
-                          int64_t cs_sw, int dtype, int64_t B, int64_t Hq, int64_t K, void* out, hipStream_t stream) {
+int kvp_qproj_rope_launch(const KvpHidden& x, const KvpRope& r, int dtype, int64_t B, int64_t Hq, void* out, hipStream_t stream) {
     QprojArgs a;
-    a.x = static_cast<const char*>(x); a.x_sb = x_sb * 2; a.x_sw = x_sw * 2;
-    a.w = static_cast<const char*>(w);
-    a.cosp = cosp; a.sinp = sinp; a.cs_sb = cs_sb; a.cs_sw = cs_sw;
-    a.out = out; a.Hq = (uint32_t)Hq; a.K = (uint32_t)K;
+    a.x = static_cast<const char*>(x.p); a.x_sb = x.sb * 2; a.x_sw = x.sw * 2;
+    a.w = static_cast<const char*>(x.wq);
+    a.cosp = r.cosp; a.sinp = r.sinp; a.cs_sb = r.sb; a.cs_sw = r.sw;
+    a.out = out; a.Hq = (uint32_t)Hq; a.K = (uint32_t)x.hidden;
     const dim3 grid((uint32_t)(Hq * 8), (uint32_t)B);
     if (dtype == KVP_BF16) KVP_LAUNCH("qproj_rope_kernel", stream, qproj_rope_kernel<KVP_BF16><<<grid, QP_THREADS, 0, stream>>>(a));
     else KVP_LAUNCH("qproj_rope_kernel", stream, qproj_rope_kernel<KVP_F16><<<grid, QP_THREADS, 0, stream>>>(a));
@@ -184,12 +182,13 @@ int kvp_qproj_rope_launch(const void* x, int64_t x_sb, int64_t x_sw, const void*
 extern "C" int kvp_snapkv_qproj_rope(const void* hidden_win, int64_t x_sb, int64_t x_sw, const void* wq, const void* cosp,
                                      const void* sinp, int64_t cs_sb, int64_t cs_sw, int dtype, int64_t B, int64_t Hq, int64_t W,
                                      int64_t D, int64_t hidden, void* q_rot, kvp_stream_t stream_) {
+    const KvpHidden x{hidden_win, x_sb, x_sw, wq, hidden};
+    const KvpRope r{cosp, sinp, cs_sb, cs_sw};
     KVP_CHECK_ARG(B >= 1 && Hq >= 1 && B <= 65535 && Hq * 8 < ((int64_t)1 << 31), "qproj_rope: bad shape B=%ld Hq=%ld", (long)B, (long)Hq);
     KVP_CHECK_ARG(hidden_win && wq && cosp && sinp && q_rot, "qproj_rope: null pointer");
-    if (!kvp_qproj_rope_eligible(dtype, W, D, hidden, hidden_win, x_sb, x_sw, wq, cosp, sinp, cs_sb, cs_sw)) {
+    if (!kvp_qproj_rope_eligible(dtype, W, D, x, r)) {
         kvp_set_error("qproj_rope: needs bf16/f16, W = 64, D = 128, hidden %% 256 == 0 and 16-byte aligned rows");
         return KVP_EUNSUPPORTED;
     }
-    return kvp_qproj_rope_launch(hidden_win, x_sb, x_sw, wq, cosp, sinp, cs_sb, cs_sw, dtype, B, Hq, hidden, q_rot,
-                                 static_cast<hipStream_t>(stream_));
+    return kvp_qproj_rope_launch(x, r, dtype, B, Hq, q_rot, static_cast<hipStream_t>(stream_));
 }

@@ -203,13 +203,11 @@ extern "C" int kvp_gather_kv_rerotate(const void* k, int64_t k_sb, int64_t k_sh,
                   (long)B, (long)H, (long)S, (long)D, (long)n);
     if (B * H * n == 0) return KVP_OK;
     KVP_CHECK_ARG(k && v && idx && inv_freq && k_out && v_out, "gather_rerotate: null pointer");
-    auto al16 = [](int64_t x) { return x % 16 == 0; };
+    const KvpRows kr{k, k_sb, k_sh, k_ss}, vr{v, v_sb, v_sh, v_ss};
     const bool fused = dtype != KVP_F32 && D % 16 == 0 && B * H <= 65535 && n * D < ((int64_t)1 << 31) && S < ((int64_t)1 << 31) &&
-                       al16((int64_t)(uintptr_t)k) && al16((int64_t)(uintptr_t)v) && al16((int64_t)(uintptr_t)k_out) &&
-                       al16((int64_t)(uintptr_t)v_out) && al16((int64_t)(uintptr_t)inv_freq) && al16(k_sb * 2) && al16(k_sh * 2) && al16(k_ss * 2) &&
-                       al16(v_sb * 2) && al16(v_sh * 2) && al16(v_ss * 2);
+                       kr.aligned(16, 2) && vr.aligned(16, 2) && (((uintptr_t)k_out | (uintptr_t)v_out | (uintptr_t)inv_freq) % 16) == 0;
     if (!fused) {   // any other shape / dtype: the two kernels it replaces
-        if (int rc = kvp_gather_kv(k, k_sb, k_sh, k_ss, v, v_sb, v_sh, v_ss, dtype, B, H, S, D, idx, n, k_out, v_out, stream_)) return rc;
+        if (int rc = kvp_gather_launch(kr, vr, dtype, B, H, S, D, idx, n, k_out, v_out, stream)) return rc;
         return kvp_rerotate_keys(k_out, dtype, B, H, n, D, idx, inv_freq, stream_);
     }
     GrArgs a;

@@ -85,18 +85,17 @@ __global__ __launch_bounds__(RD_THREADS) void rowdot_scalar_kernel(const typenam
 }
 
 template <int DT>
-void launch_rowdot(const void* x, uint32_t BH, uint32_t H, uint32_t S, uint32_t D, int64_t sb, int64_t sh, int64_t ss, const void* filt,
-                   int64_t f_sh, float scale, float* out, hipStream_t stream) {
+void launch_rowdot(KvpRows x, uint32_t BH, uint32_t H, uint32_t S, uint32_t D, const void* filt, int64_t f_sh, float scale, float* out,
+                   hipStream_t stream) {
     using T = typename Elem<DT>::T;
-    const T* xp = static_cast<const T*>(x);
+    const T* xp = static_cast<const T*>(x.p);
     const T* fp = static_cast<const T*>(filt);
     const size_t es = sizeof(T);
     const size_t rowbytes = (size_t)D * es;
-    const bool vec_ok = rowbytes % 16 == 0 && rowbytes <= 1024 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)filt % 16 == 0) &&
-                        (sb * es) % 16 == 0 && (sh * es) % 16 == 0 && (ss * es) % 16 == 0 && (f_sh * es) % 16 == 0;
+    const bool vec_ok = rowbytes % 16 == 0 && rowbytes <= 1024 && x.aligned(16, es) && ((uintptr_t)filt % 16 == 0) && (f_sh * es) % 16 == 0;
     if (!vec_ok) {
         const uint32_t bx = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)S + RD_THREADS - 1) / RD_THREADS, 1024));
-        KVP_LAUNCH("rowdot_scalar_kernel", stream, rowdot_scalar_kernel<DT><<<dim3(bx, BH), RD_THREADS, 0, stream>>>(xp, H, S, sb, sh, ss, fp, f_sh, D, scale, out));
+        KVP_LAUNCH("rowdot_scalar_kernel", stream, rowdot_scalar_kernel<DT><<<dim3(bx, BH), RD_THREADS, 0, stream>>>(xp, H, S, x.sb, x.sh, x.ss, fp, f_sh, D, scale, out));
         return;
     }
     const uint32_t chunks = (uint32_t)(rowbytes / 16);
@@ -109,7 +108,7 @@ void launch_rowdot(const void* x, uint32_t BH, uint32_t H, uint32_t S, uint32_t 
     const uint32_t bx = (uint32_t)std::max<uint64_t>(1, std::min(bx_full, bx_cap));
 #define KVP_RD_CASE(L)                                                                                                                  \
     case L:                                                                                                                             \
-        KVP_LAUNCH("rowdot_vec_kernel", stream, rowdot_vec_kernel<DT, L><<<dim3(bx, BH), RD_THREADS, 0, stream>>>(xp, H, S, sb, sh, ss, fp, f_sh, chunks, scale, out)); \
+        KVP_LAUNCH("rowdot_vec_kernel", stream, rowdot_vec_kernel<DT, L><<<dim3(bx, BH), RD_THREADS, 0, stream>>>(xp, H, S, x.sb, x.sh, x.ss, fp, f_sh, chunks, scale, out)); \
         break;
     switch (lpr) {
         KVP_RD_CASE(1) KVP_RD_CASE(2) KVP_RD_CASE(4) KVP_RD_CASE(8) KVP_RD_CASE(16) KVP_RD_CASE(32) KVP_RD_CASE(64)
@@ -128,7 +127,7 @@ extern "C" int kvp_rowdot_score(const void* x, int dtype, int64_t B, int64_t H, 
     KVP_CHECK_ARG(x && filt && out, "rowdot: null pointer");
     KVP_CHECK_ARG(S < ((int64_t)1 << 31) && B * H <= 65535, "rowdot: shape too large (S=%ld, B*H=%ld)", (long)S, (long)(B * H));
     const uint32_t BH = (uint32_t)(B * H);
-    KVP_DISPATCH_DTYPE(dtype, launch_rowdot<DT>(x, BH, (uint32_t)H, (uint32_t)S, (uint32_t)D, sb, sh, ss, filt, f_sh, scale, out, stream));
+    KVP_DISPATCH_DTYPE(dtype, launch_rowdot<DT>({x, sb, sh, ss}, BH, (uint32_t)H, (uint32_t)S, (uint32_t)D, filt, f_sh, scale, out, stream));
     KVP_CHECK_LAUNCH("rowdot");
     return KVP_OK;
 }

@@ -220,8 +220,7 @@ int launch_rownorm(const void* x, PlaneMap map, uint32_t BH, uint32_t D, float s
     const T* xp = static_cast<const T*>(x);
     const size_t es = sizeof(T);
     const size_t rowbytes = (size_t)D * es;
-    const bool vec_ok = rowbytes % 16 == 0 && ((uintptr_t)x % 16 == 0) && (map.sb * es) % 16 == 0 &&
-                        (map.sh * es) % 16 == 0 && (map.ss * es) % 16 == 0;
+    const bool vec_ok = rowbytes % 16 == 0 && KvpRows{x, map.sb, map.sh, map.ss}.aligned(16, es);
     if (!vec_ok) {
         const uint32_t bx = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)map.S + RN_THREADS - 1) / RN_THREADS, 1024));
         KVP_LAUNCH("rownorm_scalar_kernel", stream, rownorm_scalar_kernel<DT><<<dim3(bx, BH), RN_THREADS, 0, stream>>>(xp, map, D, scale, out));
@@ -299,9 +298,8 @@ static int kvp_rowsumsq_launch(KvpRows x, int dtype, int64_t B, int64_t H, int64
 int kvp_rowsumsq2_launch(KvpRows kr, KvpRows vr, int dtype, int64_t B, int64_t H, int64_t S, int64_t D, float* out_k, float* out_v, hipStream_t stream) {
     const void *k = kr.p, *v = vr.p;
     const int64_t es = kvp_elem_size(dtype);
-    auto al = [&](const KvpRows& r) { return ((uintptr_t)r.p % 16) == 0 && (r.sb * es) % 16 == 0 && (r.sh * es) % 16 == 0 && (r.ss * es) % 16 == 0; };
     const bool fast = (dtype == KVP_BF16 || dtype == KVP_F16) && D * es == 256 && B * H >= 1 && B * H <= 65535 && S >= 1 && S < ((int64_t)1 << 31) &&
-                      al(kr) && al(vr) && k && v && out_k && out_v;
+                      kr.aligned(16, es) && vr.aligned(16, es) && k && v && out_k && out_v;
     if (!fast) {
         if (int rc = kvp_rowsumsq_launch(kr, dtype, B, H, S, D, out_k, stream)) return rc;
         return kvp_rowsumsq_launch(vr, dtype, B, H, S, D, out_v, stream);

@@ -334,29 +334,23 @@ struct SnapWs {
 
 SnapWs carve_snap_ws(void* ws, int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t W, int64_t D) {
     SnapWs w;
-    size_t off = 0;
-    char* base = static_cast<char*>(ws);
-    auto take = [&](size_t bytes) {
-        void* p = base ? base + off : nullptr;
-        off += kvp_align_up(bytes, 256);
-        return p;
-    };
+    KvpArena ar(ws);
     // generic kernels: one workgroup per 512 keys; MFMA kernels: up to one per 128-key tile, never more than 256 (snapkv_mfma_nchunk)
     const int64_t nchunk_max = std::max<int64_t>((S + SK_CHUNK_GENERIC - 1) / SK_CHUNK_GENERIC, std::min<int64_t>((S + 127) / 128, 256));
     const size_t rows = (size_t)B * Hq * snapkv_wp((uint32_t)W);   // the MFMA path keeps its statistics per PADDED window row (snapkv_internal.h)
-    w.bmax = (float*)take((size_t)std::max<int64_t>(4096, B * Hkv) * 4);
-    w.part_m = (float*)take(rows * nchunk_max * 4);
-    w.part_z = (float*)take(rows * nchunk_max * 4);
-    w.rowstat = (float*)take(rows * 4);
-    w.colsum = (float*)take((size_t)B * Hkv * (S > W ? S - W : 0) * 4);
+    w.bmax = ar.take<float>((size_t)std::max<int64_t>(4096, B * Hkv));
+    w.part_m = ar.take<float>(rows * nchunk_max);
+    w.part_z = ar.take<float>(rows * nchunk_max);
+    w.rowstat = ar.take<float>(rows);
+    w.colsum = ar.take<float>((size_t)B * Hkv * (S > W ? S - W : 0));
     const int64_t ngb = (Hq / std::max<int64_t>(1, Hkv) + 3) / 4;   // group-blocks of four q-heads per kv-head (MFMA pass 2: one column-sum slab each)
-    w.colsum2 = ngb > 1 ? (float*)take((size_t)(ngb - 1) * B * Hkv * (S > W ? S - W : 0) * 4) : nullptr;
-    w.colsumx = W > 64 ? (float*)take((size_t)B * Hkv * (S > W ? S - W : 0) * 4) : nullptr;
-    w.qrot = take((size_t)B * Hq * W * D * 4);
+    w.colsum2 = ngb > 1 ? ar.take<float>((size_t)(ngb - 1) * B * Hkv * (S > W ? S - W : 0)) : nullptr;
+    w.colsumx = W > 64 ? ar.take<float>((size_t)B * Hkv * (S > W ? S - W : 0)) : nullptr;
+    w.qrot = ar.take<char>((size_t)B * Hq * W * D * 4);   // (in the input dtype; sized for float32)
     // (planes * nchunk <= max(planes, 256): one resident round of workgroups; planes = B * Hkv * group-blocks)
     const size_t nwg = (size_t)std::max<int64_t>(B * Hkv * ngb, 256);
-    w.p1_ticks = (uint32_t*)take(nwg * 4);
-    w.total_bytes = off;
+    w.p1_ticks = ar.take<uint32_t>(nwg);
+    w.total_bytes = ar.bytes();
     return w;
 }
 
@@ -451,10 +445,7 @@ int snapkv_score_impl(const SnapCall& c, KvpRows q) {
             const void* fns[2] = {nullptr, nullptr};
             KVP_DISPATCH_DTYPE(dtype, fns[0] = (const void*)snapkv_p1_generic<DT>; fns[1] = (const void*)snapkv_p2_generic<DT>);
             for (int i = 0; i < 2; ++i)
-                if (hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(lds1, lds2)) != hipSuccess) {
-                    kvp_set_error("snapkv: cannot raise the dynamic LDS limit to %zu bytes (D=%ld, W=%ld)", std::max(lds1, lds2), (long)D, (long)W);
-                    return KVP_EHIP;
-                }
+                if (int rc = kvp_raise_dynamic_lds("snapkv", fns[i], std::max(lds1, lds2))) return rc;
         }
         const dim3 g1(nchunk, (uint32_t)Hq, (uint32_t)B);
         const uint32_t nchunk2 = (uint32_t)((S - W + SK_CHUNK_GENERIC - 1) / SK_CHUNK_GENERIC);
@@ -484,7 +475,7 @@ float snapkv_pool_scale(int64_t Hq, int64_t Hkv, int64_t W, int kernel_size) {
     return (float)(1.0 / ((double)(Hq / Hkv) * (double)W * (double)kernel_size));
 }
 
-int snapkv_score_rope_impl(const SnapCall& c, KvpRows q, const SnapRope& r) {
+int snapkv_score_rope_impl(const SnapCall& c, KvpRows q, const KvpRope& r) {
     const int64_t B = c.B, Hq = c.Hq, W = c.W, D = c.D;
     const int dtype = c.dtype;
     hipStream_t stream = c.stream;
@@ -496,14 +487,13 @@ int snapkv_score_rope_impl(const SnapCall& c, KvpRows q, const SnapRope& r) {
     if (int rc = kvp_check_workspace("snapkv", c.ws, c.ws_bytes, w.total_bytes)) return rc;
     const uint32_t total = (uint32_t)(B * Hq * W * (D / 2));
     const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((total + SK_THREADS - 1) / SK_THREADS, 2048));
-    const bool rvec = dtype != KVP_F32 && D % 16 == 0 && ((uintptr_t)q.p % 16) == 0 && ((uintptr_t)r.cosp % 16) == 0 && ((uintptr_t)r.sinp % 16) == 0 &&
-                      ((uintptr_t)w.qrot % 16) == 0 && (q.sb * 2) % 16 == 0 && (q.sh * 2) % 16 == 0 && (q.ss * 2) % 16 == 0 && (r.cs_sb * 2) % 16 == 0 && (r.cs_sw * 2) % 16 == 0;
+    const bool rvec = dtype != KVP_F32 && D % 16 == 0 && q.aligned(16, 2) && r.aligned(16, 2) && ((uintptr_t)w.qrot % 16) == 0;
     const uint32_t vblocks = std::max<uint32_t>(1, std::min<uint32_t>((total / 8 + SK_THREADS - 1) / SK_THREADS, 2048));
     // (KERNEL, grid) for one dtype; the vector kernel exists for the 2-byte dtypes only, so its ladder has two rungs
 #define KVP_SK_ROPE(KERNEL, NBLK, DT)                                                                                        \
     KVP_LAUNCH("snapkv_rope_kernel", stream, KERNEL<DT><<<NBLK, SK_THREADS, 0, stream>>>(                                      \
         static_cast<const Elem<DT>::T*>(q.p), q.sb, q.sh, q.ss, static_cast<const Elem<DT>::T*>(r.cosp),                       \
-        static_cast<const Elem<DT>::T*>(r.sinp), r.cs_sb, r.cs_sw, (uint32_t)B, (uint32_t)Hq, (uint32_t)W, (uint32_t)D,        \
+        static_cast<const Elem<DT>::T*>(r.sinp), r.sb, r.sw, (uint32_t)B, (uint32_t)Hq, (uint32_t)W, (uint32_t)D,        \
         static_cast<Elem<DT>::T*>(w.qrot)));
     if (rvec && dtype == KVP_F16) { KVP_SK_ROPE(snapkv_rope_vec_kernel, vblocks, KVP_F16) }
     else if (rvec) { KVP_SK_ROPE(snapkv_rope_vec_kernel, vblocks, KVP_BF16) }
@@ -514,16 +504,16 @@ int snapkv_score_rope_impl(const SnapCall& c, KvpRows q, const SnapRope& r) {
 }
 
 // window queries from the hidden states (fused q_proj + RoPE, qproj.hip), then as above
-int snapkv_score_hidden_impl(const SnapCall& c, const SnapHidden& x, const SnapRope& r) {
+int snapkv_score_hidden_impl(const SnapCall& c, const KvpHidden& x, const KvpRope& r) {
     if (int rc = check_common(c)) return rc;
     KVP_CHECK_ARG(x.p && x.wq && r.cosp && r.sinp && c.k.p && c.scores, "snapkv: null pointer");
-    if (!kvp_qproj_rope_eligible(c.dtype, c.W, c.D, x.hidden, x.p, x.sb, x.sw, x.wq, r.cosp, r.sinp, r.cs_sb, r.cs_sw)) {
+    if (!kvp_qproj_rope_eligible(c.dtype, c.W, c.D, x, r)) {
         kvp_set_error("snapkv: fused q_proj needs bf16/f16, W = 64, D = 128, hidden %% 256 == 0, 16-byte aligned rows");
         return KVP_EUNSUPPORTED;
     }
     SnapWs w = carve_snap_ws(c.ws, c.B, c.Hq, c.Hkv, c.S, c.W, c.D);
     if (int rc = kvp_check_workspace("snapkv", c.ws, c.ws_bytes, w.total_bytes)) return rc;
-    if (int rc = kvp_qproj_rope_launch(x.p, x.sb, x.sw, x.wq, r.cosp, r.sinp, r.cs_sb, r.cs_sw, c.dtype, c.B, c.Hq, x.hidden, w.qrot, c.stream)) return rc;
+    if (int rc = kvp_qproj_rope_launch(x, r, c.dtype, c.B, c.Hq, w.qrot, c.stream)) return rc;
     return snapkv_score_impl(c, qrot_rows(w, c));
 }
 

@@ -59,8 +59,6 @@ struct SnapCall {
     bool count_norm = false;        // FINCH: window row w weighted by its S - W + w visible keys
     int finish = SNAP_FINISH_FULL;  // what happens after the two attention passes
 };
-struct SnapRope { const void *cosp, *sinp; int64_t cs_sb, cs_sw; };                        // the window's rotary tables [1 or B, W, D]
-struct SnapHidden { const void* p; int64_t sb, sw; const void* wq; int64_t hidden; };      // hidden states of the window [B, W, hidden] + q_proj.weight
 // Defined in snapkv.hip, used by the fused compress (compress.hip).  q: PRE-RoPE window queries [B,Hq,W,D]
-int snapkv_score_rope_impl(const SnapCall& c, KvpRows q, const SnapRope& r);
-int snapkv_score_hidden_impl(const SnapCall& c, const SnapHidden& x, const SnapRope& r);
+int snapkv_score_rope_impl(const SnapCall& c, KvpRows q, const KvpRope& r);
+int snapkv_score_hidden_impl(const SnapCall& c, const KvpHidden& x, const KvpRope& r);

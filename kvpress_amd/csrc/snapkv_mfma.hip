@@ -592,9 +592,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void snapkv_p2_mfma(SnapArgs a, uint
 bool snapkv_mfma_eligible(const SnapArgs& a, int dtype) {
     if (dtype != KVP_BF16 && dtype != KVP_F16) return false;
     if ((a.D != 256 && a.D != 128 && a.D != 96 && a.D != 64) || a.W < 1 || a.W > 4096 || a.G > 16) return false;   // (any window: blocks of 64 rows, snapkv_internal.h)
-    auto al8 = [](int64_t x) { return x % 8 == 0; };
-    if (((uintptr_t)a.q % 16) || ((uintptr_t)a.k % 16)) return false;
-    return al8(a.q_sb) && al8(a.q_sh) && al8(a.q_sw) && al8(a.k_sb) && al8(a.k_sh) && al8(a.k_ss);
+    return KvpRows{a.q, a.q_sb, a.q_sh, a.q_sw}.aligned(16, 2) && KvpRows{a.k, a.k_sb, a.k_sh, a.k_ss}.aligned(16, 2);
 }
 
 // Workgroups per (batch, kv-head, group-block).  The grid is sized to ONE resident round (1 workgroup of 8 waves

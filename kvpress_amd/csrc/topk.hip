@@ -592,7 +592,7 @@ int topk_select_impl(const float* scores, int64_t R, int64_t S, int64_t row_stri
     }
     // long rows: the whole select in one launch (topk_cluster.hip); rc 1 = the device cannot hold its grid -> the passes below
     if (topk_cluster_eligible(R, S)) {
-        const int rc = topk_cluster_select(TOPK_CLUSTER_SCORES, scores, row_stride, 1.f, nullptr, 0, 0, 0, 0, 1, 0.f, R, S, k, idx, idx_stride, tail_start,
+        const int rc = topk_cluster_select(TOPK_CLUSTER_SCORES, scores, row_stride, 1.f, KvpRows{}, 0, 1, 0.f, R, S, k, idx, idx_stride, tail_start,
                                            tail_n, w, hist1_ready, stream, nseg, seg_len, pos_base);
         if (rc != 1) return rc;
     }

@@ -922,8 +922,7 @@ bool topk_cluster_eligible(int64_t R, int64_t S) {
 }
 
 // returns KVP_OK, an error, or 1 = "not launched" (the device cannot hold the grid: the caller takes the (chunk, row) passes)
-int topk_cluster_select(int mode, const float* scores, int64_t row_stride, float inv, const void* x, int dtype, int64_t x_sb, int64_t x_sh,
-                        int64_t x_ss, int64_t H, float scale, int64_t R, int64_t S, int64_t k, int32_t* idx, int64_t idx_stride,
+int topk_cluster_select(int mode, const float* scores, int64_t row_stride, float inv, KvpRows x, int dtype, int64_t H, float scale, int64_t R, int64_t S, int64_t k, int32_t* idx, int64_t idx_stride,
                         uint32_t tail_start, uint32_t tail_n, const TopkWs& w, bool hist1_ready, hipStream_t stream, uint32_t nseg,
                         uint32_t seg_len, uint32_t pos_base) {
     ClusterArgs a;
@@ -933,7 +932,7 @@ int topk_cluster_select(int mode, const float* scores, int64_t row_stride, float
     a.idx = idx; a.idx_stride = idx_stride;
     a.tail_start = tail_start; a.tail_n = tail_n; a.nseg = nseg; a.seg_len = seg_len; a.pos_base = pos_base;
     a.ws0 = w.base; a.wsR = w.lay_R; a.ws_ntab = w.lay_ntab;
-    a.x = x; a.x_sb = x_sb; a.x_sh = x_sh; a.x_ss = x_ss; a.H = (uint32_t)std::max<int64_t>(1, H); a.scale = scale;
+    a.x = x.p; a.x_sb = x.sb; a.x_sh = x.sh; a.x_ss = x.ss; a.H = (uint32_t)std::max<int64_t>(1, H); a.scale = scale;
     int rc;
     switch (mode) {
         case TOPK_CLUSTER_POOL5: rc = launch_per<TC_POOL5, false>(a, stream); break;

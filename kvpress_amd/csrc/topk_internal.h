@@ -154,8 +154,7 @@ bool topk_row_eligible(int64_t S);
 enum { TOPK_CLUSTER_SCORES = 0, TOPK_CLUSTER_POOL5 = 1, TOPK_CLUSTER_KNORM = 2 };
 bool topk_cluster_eligible(int64_t R, int64_t S);
 bool topk_cluster_launchable();   // the current device can hold the cluster kernel's 256 workgroups at once
-int topk_cluster_select(int mode, const float* scores, int64_t row_stride, float inv, const void* x, int dtype, int64_t x_sb, int64_t x_sh,
-                        int64_t x_ss, int64_t H, float scale, int64_t R, int64_t S, int64_t k, int32_t* idx, int64_t idx_stride,
+int topk_cluster_select(int mode, const float* scores, int64_t row_stride, float inv, KvpRows x, int dtype, int64_t H, float scale, int64_t R, int64_t S, int64_t k, int32_t* idx, int64_t idx_stride,
                         uint32_t tail_start, uint32_t tail_n, const TopkWs& w, bool hist1_ready, hipStream_t stream, uint32_t nseg = 1,
                         uint32_t seg_len = 0, uint32_t pos_base = 0);
 // should a score-writing kernel accumulate the first histogram for a select over S columns?  (S > 16384)

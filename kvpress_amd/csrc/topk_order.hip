@@ -343,10 +343,7 @@ int launch_psrs(const OrderArgs& a, int mode, int64_t R, hipStream_t stream) {
     const size_t lds = (size_t)(2 * 1024 * E + OS_MAX_TILES * (1024 * E / OS_GROUP)) * 8;
     static bool raised[2] = {false, false};                      // (per instantiation; the attribute is per function, set once)
     if (lds > 48 * 1024 && !raised[E / 4]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(order_buckets_kernel<E>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            kvp_set_error("topk(order): cannot raise the dynamic LDS limit to %zu bytes", lds);
-            return KVP_EHIP;
-        }
+        if (int rc = kvp_raise_dynamic_lds("topk(order)", order_buckets_kernel<E>, lds)) return rc;
         raised[E / 4] = true;
     }
     KVP_LAUNCH("order_buckets_kernel", stream, (order_buckets_kernel<E><<<grid, 1024, lds, stream>>>(a)));

@@ -140,6 +140,19 @@ def test_no_hand_written_prototypes_of_other_files_functions():
     assert not bad, f"prototypes of functions defined in another .hip (declare them in kvp_host.h): {bad}"
 
 
+def test_host_plumbing_is_spelled_once():
+    """csrc/kvp_host.h holds the one workspace arena (KvpArena) and the one place that raises a kernel's dynamic LDS limit
+    (kvp_raise_dynamic_lds): no .hip carves a workspace with a local `take` lambda, and nothing under csrc/ but kvp_host.h names the
+    attribute"""
+    csrc = os.path.join(ROOT, "kvpress_amd", "csrc")
+    files = [os.path.join(d, f) for d, _, fs in os.walk(csrc) for f in fs if f.endswith((".hip", ".h", ".inc"))]
+    assert len([f for f in files if f.endswith(".hip")]) >= 20
+    raises = sorted(os.path.relpath(f, csrc) for f in files if "hipFuncAttributeMaxDynamicSharedMemorySize" in open(f).read())
+    assert raises == ["kvp_host.h"], f"the dynamic LDS limit is raised outside kvp_raise_dynamic_lds: {raises}"
+    takes = sorted(os.path.relpath(f, csrc) for f in files if f.endswith(".hip") and re.search(r"\bauto\s+take\s*=\s*\[", open(f).read()))
+    assert not takes, f"hand-rolled workspace carvers (use KvpArena): {takes}"
+
+
 C_TYPES = {"void": None, "char": ctypes.c_char, "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
            "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double}
 
