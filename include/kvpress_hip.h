@@ -372,6 +372,28 @@ int kvp_cam_merge_prune(const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss,
                         const float* mask, int dtype, int64_t B, int64_t H, int64_t S, int64_t T, int64_t M, int64_t D,
                         int64_t merge_budget, void* k_out, void* v_out, float* attn_out, kvp_stream_t stream);
 
+/* ---- CriticalKVPress.vwl1norm + the rescale (kvpress/presses/criticalkv_press.py:57-76, :87; CriticalAdaKVPress :174-175) -------------
+ * values: [B,Hkv,S,D] (element strides); wo: o_proj.weight [hidden, Hq*D] in the same dtype, rows wo_ld elements apart (a bias is ignored,
+ * as the reference ignores it).  With G = Hq / Hkv
+ *     norm[b,k,s] = (1/G) sum_{g<G} sum_{c<hidden} | sum_{d<D} v[b,k,s,d] * wo[c, (k*G + g)*D + d] |
+ * -- the reference's per-head `V_h @ Wo_h` of [S, hidden] (:69), its L1 norm (:70) and the mean over the group (:75) without the
+ * intermediate.  scores_in NULL: out = norm; else out = (scores_in + eps) * norm, float32, the sum rounded before the product (:87);
+ * scores_in: float32 [B*Hkv, S], rows scores_stride elements apart; out: float32 [B*Hkv, S] contiguous, may alias scores_in.
+ * bf16 / f16 with D in {64,96,128,256} and 16-byte aligned rows of values and wo run on the matrix cores (products exact, float32
+ * accumulation and sums; the value rows of a token tile stay in registers for all G heads and every row of wo; nothing of size
+ * [S, hidden] or [Hq, S] is stored); everything else (float32, other D, unaligned rows) on a generic kernel.  hidden and S need not be
+ * multiples of any tile.  The workspace is empty today (the query returns 0; ws may be NULL).  Bit-identical from run to run. */
+size_t kvp_vwl1norm_workspace_bytes(int64_t B, int64_t Hq, int64_t Hkv, int64_t S, int64_t D, int64_t hidden);
+int kvp_vwl1norm_rescale(const void* values, int64_t v_sb, int64_t v_sh, int64_t v_ss, int dtype, const void* wo, int64_t wo_ld, int64_t B,
+                         int64_t Hq, int64_t Hkv, int64_t S, int64_t D, int64_t hidden, const float* scores_in, int64_t scores_stride,
+                         float eps, float* out, void* ws, size_t ws_bytes, kvp_stream_t stream);
+
+/* scores[r, idx[r, j]] = value for every j < counts[r]: the per-head prefix `scatter_` of the two-stage selection
+ * (kvpress/presses/criticalkv_press.py:169-171, :177-179) on the rows of a KVP_ORDER_SCORE select.  idx int32 [R, n] contiguous; counts
+ * int32 [R] on the device, 0 <= counts[r] <= n (clamped); scores rows row_stride elements apart. */
+int kvp_scores_fill_prefix(float* scores, int64_t R, int64_t S, int64_t row_stride, const int32_t* idx, int64_t n, const int32_t* counts,
+                           float value, kvp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

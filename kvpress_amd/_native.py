@@ -105,6 +105,10 @@ SIGNATURES = {
                                    c_void_p, c_void_p]),
     "kvp_cam_merge_prune": (c_int, [c_void_p, _I64, _I64, _I64, c_void_p, _I64, _I64, _I64, c_void_p, _I64, _I64, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_int, _I64, _I64, _I64, _I64, _I64, _I64, _I64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "kvp_vwl1norm_workspace_bytes": (c_size_t, [_I64] * 6),
+    "kvp_vwl1norm_rescale": (c_int, [c_void_p, _I64, _I64, _I64, c_int, c_void_p, _I64, _I64, _I64, _I64, _I64, _I64, _I64, c_void_p, _I64,
+                                     c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "kvp_scores_fill_prefix": (c_int, [c_void_p, _I64, _I64, _I64, c_void_p, _I64, c_void_p, c_float, c_void_p]),
 }
 # include/kvpress_hip_lab.h: measurement / test aids of the same library (bench.py, tools/, the select's residency tests)
 LAB_SIGNATURES = {
@@ -831,6 +835,61 @@ def cam_merge_prune(keys: torch.Tensor, values: torch.Tensor, running: torch.Ten
         _call("kvp_cam_merge_prune", *_tensor(keys), *_tensor(values), *_tensor(running, 2), _p(kept), _p(cand), _p(start), _p(mask),
               _DTYPES[keys.dtype], B, H, S, T, M, D, int(merge_budget), _p(ko), _p(vo), _p(ao), _stream(keys))
     return ko, vo, ao
+
+
+# CriticalKVPress / CriticalAdaKVPress (criticalkv_press.py:57-92, :137-194)
+def _vwl1(values: torch.Tensor, wo: torch.Tensor, num_heads: int, scores: Optional[torch.Tensor], eps: float, out: torch.Tensor):
+    values = _rows(values)
+    B, Hkv, S, D = values.shape
+    wo = _dev(wo)
+    Hq = int(num_heads)
+    if Hq % Hkv != 0:
+        raise KvpressHipError(f"kvp_vwl1norm_rescale: Hq % Hkv != 0 ({Hq}, {Hkv})")
+    assert wo.dim() == 2 and wo.shape[1] == Hq * D, (wo.shape, Hq, D)
+    if wo.dtype != values.dtype or wo.device != values.device:
+        wo = wo.to(device=values.device, dtype=values.dtype)
+    if wo.stride(1) != 1:
+        wo = wo.contiguous()
+    with _on_device(values.device):
+        nws = _ws_bytes("kvp_vwl1norm_workspace_bytes", B, Hq, Hkv, S, D, wo.shape[0])   # 0 today: no allocation
+        ws = _ws(nws, values) if nws else None
+        _call("kvp_vwl1norm_rescale", *_tensor(values), _DTYPES[values.dtype], *_tensor(wo, 1), B, Hq, Hkv, S, D, wo.shape[0],
+              _p(scores), S, float(eps), _p(out), _p(ws), nws, _stream(values))
+    return out
+
+
+def vwl1norm(values: torch.Tensor, wo: torch.Tensor, num_heads: int) -> torch.Tensor:
+    """CriticalKVPress.vwl1norm (criticalkv_press.py:57-76): float32 [B,Hkv,S], the L1 norm of every value row [B,Hkv,S,D] pushed through
+    o_proj.weight ``wo`` [hidden, num_heads * D] (a row-strided view passes through), averaged over the query heads of its kv head.
+    ``wo`` is read in place when it has the values' dtype and device (a model's own cache: always); otherwise -- a float32 cache over a
+    bf16 module -- the whole weight is converted and copied on EVERY call."""
+    B, Hkv, S, _ = values.shape
+    return _vwl1(values, wo, num_heads, None, 0.0, torch.empty((B, Hkv, S), dtype=torch.float32, device=values.device))
+
+
+def vwl1norm_rescale_(scores: torch.Tensor, values: torch.Tensor, wo: torch.Tensor, num_heads: int, eps: float) -> torch.Tensor:
+    """In place: scores <- (scores + eps) * vwl1norm(values, wo, num_heads) in float32, in that order (criticalkv_press.py:87);
+    scores float32 [B,Hkv,S] contiguous."""
+    _dev(scores), _dev(values)
+    assert scores.dtype == torch.float32 and scores.is_contiguous() and tuple(scores.shape) == tuple(values.shape[:3]), (
+        scores.shape, scores.dtype, values.shape)
+    return _vwl1(values, wo, num_heads, scores, eps, scores)
+
+
+def scores_fill_prefix_(scores: torch.Tensor, idx: torch.Tensor, counts: torch.Tensor, value: float) -> torch.Tensor:
+    """In place: scores[r, idx[r, j]] = value for j < counts[r] (criticalkv_press.py:169-171, :177-179): float32 scores [..., S]
+    contiguous, int32 idx [..., n] (the rows of an ORDER_SCORE select), counts one integer per row on the device."""
+    _dev(scores)
+    assert scores.dtype == torch.float32 and scores.is_contiguous()
+    S = scores.shape[-1]
+    idx = idx.to(torch.int32).contiguous()
+    n = idx.shape[-1]
+    R = scores.numel() // S if S else 0
+    counts = counts.to(device=scores.device, dtype=torch.int32).contiguous()
+    assert idx.numel() == R * n and counts.numel() == R, (idx.shape, counts.shape, scores.shape)
+    with _on_device(scores.device):
+        _call("kvp_scores_fill_prefix", _p(scores), R, S, S, _p(idx), n, _p(counts), float(value), _stream(scores))
+    return scores
 
 
 # ---- the q_proj eligibility logic ---------------------------------------------------------------------------------------------------

@@ -31,7 +31,11 @@ ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-fvisibility=hidden", "-fvisibility-inlines-hidden"]
 # MFMA results straight into VGPRs (gfx950 has a unified register file): the softmax epilogues read every
 # accumulator element with VALU ops, and v_accvgpr_read was 16 of their 73 instructions per 16 logits.
-FILE_FLAGS = {"snapkv_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "ea_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+FILE_FLAGS = {"snapkv_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "ea_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+              # vwl1.hip: the abs-sum reads all 16 accumulators with the |x| source modifier.  Left to itself the SLP vectoriser packs
+              # those adds into v_pk_add_f32 behind v_and masks (more instructions beside the MFMAs, not fewer) and the D = 128
+              # kernel then spills at two waves per SIMD.
+              "vwl1.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"]}
 
 
 def flags_for(src: str):
