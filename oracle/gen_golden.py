@@ -28,6 +28,7 @@ os.environ["PYTHONDONTWRITEBYTECODE"] = "1"
 sys.dont_write_bytecode = True
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(REPO, "tests", "golden")
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
 
@@ -47,8 +48,27 @@ def _install_shims():
     sys.path.insert(0, "/root/reference")
 
 
-def main(argv):
+# ---- the opening and the closing of every oracle/gen_golden*.py (each imports this module: it lies next to them) -------
+def setup():
+    """the reference package (behind its shims), the repository's packages and the input modules of tests/ on the path"""
+    for p in (os.path.join(REPO, "tests"), REPO):
+        if p not in sys.path:
+            sys.path.insert(0, p)
     _install_shims()
+
+
+def save(name, arrays):
+    """write tests/golden/<name>.npz and print its path and size"""
+    import numpy as np
+
+    os.makedirs(GOLDEN, exist_ok=True)
+    path = os.path.join(GOLDEN, f"{name}.npz")
+    np.savez_compressed(path, **arrays)
+    print(f"{path}: {os.path.getsize(path)} bytes")
+
+
+def main(argv):
+    setup()
     import numpy as np
     import torch
     from kvpress import (CURPress, ExpectedAttentionPress, KeyDiffPress, KnormPress, LagKVPress, ObservedAttentionPress, PyramidKVPress,  # the reference
@@ -58,8 +78,6 @@ def main(argv):
     import _inputs
 
     torch.manual_seed(0)
-    outdir = os.path.join(REPO, "tests", "golden")
-    os.makedirs(outdir, exist_ok=True)
     names = argv or list(_inputs.CASES)
     for name in names:
         s = _inputs.make_case(name)
@@ -134,9 +152,8 @@ def main(argv):
                         idx = sc_r.topk(n, dim=-1).indices.sort(dim=-1).values
                         out[f"idx_f32_{i}"] = idx.numpy().astype(np.int32)
         out.update(captured)
-        path = os.path.join(outdir, f"{name}.npz")
-        np.savez_compressed(path, **out)
-        print(f"{name}: wrote {os.path.getsize(path)} bytes; nkept={[int(out[f'nkept_{i}']) for i in range(len(s['ratios']))]}")
+        save(name, out)
+        print(f"  nkept={[int(out[f'nkept_{i}']) for i in range(len(s['ratios']))]}")
 
 
 if __name__ == "__main__":

@@ -2,7 +2,7 @@
 """Reference outputs of CAMPress: runs the REAL reference (NVIDIA/kvpress, put on the path by oracle/gen_golden.py's shims) on the host CPU
 over the seeded inputs of tests/_cam_inputs.py and writes tests/golden/cam_*.npz.
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_cam.py [case ...]
+    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden_cam.py [case ...]
 
 Per case and run ("o32": module and tensors in float32; "nat": the case's model dtype), from one direct call of compress() with the
 layer's step count and running attention sum preset: the kept and the merge-candidate positions (the two arguments of its
@@ -10,21 +10,13 @@ torch.searchsorted call), the merge probabilities and the mask (input and output
 running sum A' (`*_kept`, `*_cand`, `*_prob`, `*_mask`, `*_k`, `*_v`, `*_a`); and the per-step attention of the newest token from its
 two static methods (`*_attn`, [B,Hkv,S]).
 """
-import os
 import sys
 
-os.environ["PYTHONDONTWRITEBYTECODE"] = "1"
-sys.dont_write_bytecode = True
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tests"))
-sys.path.insert(0, os.path.join(REPO, "oracle"))
-sys.path.insert(0, REPO)
+import gen_golden  # (next to this script) the generators' shared opening and closing
 
 
 def main(argv):
-    from gen_golden import _install_shims
-
-    _install_shims()
+    gen_golden.setup()
     import numpy as np
     import torch
     from kvpress import CAMPress, KnormPress  # the reference
@@ -49,7 +41,6 @@ def main(argv):
         def __exit__(self, *exc):
             setattr(torch, self.name, self.orig)
 
-    outdir = os.path.join(REPO, "tests", "golden")
     for name in argv or list(CI.CASES):
         s = CI.make_case(name)
         out = {}
@@ -78,9 +69,7 @@ def main(argv):
             out[f"{run}_k"] = k2.float().numpy()
             out[f"{run}_v"] = v2.float().numpy()
             out[f"{run}_a"] = press._running_attn_sum[0].float().numpy()
-        path = os.path.join(outdir, name + ".npz")
-        np.savez_compressed(path, **out)
-        print(f"{path}: {os.path.getsize(path)} bytes")
+        gen_golden.save(name, out)
 
 
 if __name__ == "__main__":

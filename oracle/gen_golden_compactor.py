@@ -3,28 +3,20 @@
 (NVIDIA/kvpress, put on the path by oracle/gen_golden.py's shims, as the oracle/gen_golden*.py scripts do) on the host CPU over the seeded inputs of
 tests/_compactor_inputs.py and writes tests/golden/cpt_*.npz.
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_compactor.py [case ...]
+    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden_compactor.py [case ...]
 
 Per case and run ("o32": module and tensors in float32; "nat": the case's model dtype): the sketch the reference drew (recorded by
 wrapping torch.randn: the raw draw `*_phi_draw`, BEFORE the reference's `* (1 / sqrt(k))`; tests/_compactor_inputs.phi_from_draw
 applies that scaling exactly as leverage_press.py:68-75 does, and a test that injects the draw as torch.randn's result reproduces Phi), the raw and z-scored scores of NonCausalAttn and Leverage, CompactorPress's scores and the positions its
 compress() keeps per ratio.
 """
-import os
 import sys
 
-os.environ["PYTHONDONTWRITEBYTECODE"] = "1"
-sys.dont_write_bytecode = True
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tests"))
-sys.path.insert(0, os.path.join(REPO, "oracle"))
-sys.path.insert(0, REPO)
+import gen_golden  # (next to this script) the generators' shared opening and closing
 
 
 def main(argv):
-    from gen_golden import _install_shims
-
-    _install_shims()
+    gen_golden.setup()
     import numpy as np
     import torch
     import torch.nn.functional as F
@@ -51,7 +43,6 @@ def main(argv):
         def __exit__(self, *exc):
             torch.randn = self.orig
 
-    outdir = os.path.join(REPO, "tests", "golden")
     for name in argv or list(CI.CASES):
         s = CI.make_case(name)
         out = {}
@@ -91,9 +82,7 @@ def main(argv):
                     out[tag + "_scores"] = sc.float().numpy()
                     n = int(s["S"] * (1 - ratio))
                     out[tag + "_kept"] = np.sort(sc.float().topk(n, dim=-1).indices.numpy(), axis=-1).astype(np.int32)
-        path = os.path.join(outdir, name + ".npz")
-        np.savez_compressed(path, **out)
-        print(f"{path}: {os.path.getsize(path)} bytes")
+        gen_golden.save(name, out)
 
 
 if __name__ == "__main__":

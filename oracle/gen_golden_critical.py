@@ -2,7 +2,7 @@
 """Reference outputs of CriticalKVPress / CriticalAdaKVPress: runs the REAL reference (NVIDIA/kvpress, put on the path by
 oracle/gen_golden.py's shims) on the host CPU over the seeded inputs of tests/_critical_inputs.py and writes tests/golden/crit_*.npz.
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_critical.py [case ...]
+    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden_critical.py [case ...]
 
 Per case, from the run with module and tensors in float32: `norm` (CriticalKVPress.vwl1norm, [B,H,S]) and `inner` (the wrapped press's
 scores); per ratio i `crit_scores_<i>` (CriticalKVPress.score) and `crit_pos_<i>` (the positions its compress() keeps, sorted, int32
@@ -14,21 +14,13 @@ The comparisons of tests/test_critical_host.py and tests/test_gpu_critical.py ar
 asserted here, on the reference's own numbers: per head and selection at most 1 % of the positions lie in its band, and the flattened budget selection
 has a relative gap above 1e-4 at its threshold (the budgets then compare exactly).
 """
-import os
 import sys
 
-os.environ["PYTHONDONTWRITEBYTECODE"] = "1"
-sys.dont_write_bytecode = True
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tests"))
-sys.path.insert(0, os.path.join(REPO, "oracle"))
-sys.path.insert(0, REPO)
+import gen_golden  # (next to this script) the generators' shared opening and closing
 
 
 def main(argv):
-    from gen_golden import _install_shims
-
-    _install_shims()
+    gen_golden.setup()
     import numpy as np
     import torch
     import kvpress as R   # the reference
@@ -54,7 +46,6 @@ def main(argv):
         def __exit__(self, *exc):
             torch.Tensor.scatter_add_ = self.orig
 
-    outdir = os.path.join(REPO, "tests", "golden")
     for name in argv or list(CI.CASES):
         s = CI.make_case(name)
         assert s["B"] == 1, "the reference's CriticalAdaKVPress fails for B > 1"
@@ -101,9 +92,7 @@ def main(argv):
                     a = CO.critical_ada(inner, norm.numpy(), r, s["alpha"], s["fsr"], CI.EPSILON)
                     assert a["band_max"] <= 0.01 * S, f"{name} r={r}: {a['band_max']} of {S} positions within 1e-3 of a CriticalAdaKV threshold"
                     assert a["budget_gap"].min() > 1e-4, f"{name} r={r}: budget threshold gap {a['budget_gap']}"
-        path = os.path.join(outdir, name + ".npz")
-        np.savez_compressed(path, **out)
-        print(f"{path}: {os.path.getsize(path)} bytes")
+        gen_golden.save(name, out)
 
 
 if __name__ == "__main__":

@@ -8,19 +8,13 @@ Per case: scores_f32 [B,H,S] and qwin_f32 (the RoPE'd question queries) of the f
 (f32 / nat = the case dtype): pos_<run>_<i> the kept positions, sorted (recovered from a VALUE tensor that stores each
 token's position) and, for the re-rotating variant, kout_<run>_<i> the re-rotated keys (float32 storage).
 """
-import os
 import sys
 
-os.environ["PYTHONDONTWRITEBYTECODE"] = "1"
-sys.dont_write_bytecode = True
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tests"))
-sys.path.insert(0, os.path.join(REPO, "oracle"))
+import gen_golden  # (next to this script) the generators' shared opening and closing
 
 
 def main(argv):
-    import gen_golden
-    gen_golden._install_shims()
+    gen_golden.setup()
     import kvpress
     import numpy as np
     import torch
@@ -29,7 +23,6 @@ def main(argv):
 
     import _inputs
 
-    outdir = os.path.join(REPO, "tests", "golden")
     for name in (argv or list(_inputs.FINCH_CASES)):
         s = _inputs.make_finch_case(name)
         out = {"ratios": np.asarray(s["ratios"], dtype=np.float64)}
@@ -56,9 +49,8 @@ def main(argv):
                         assert torch.equal(ko, keys.gather(2, pos.unsqueeze(-1).expand(-1, -1, -1, s["D"])))
                         pos = pos.gather(-1, order)
                     out[f"pos_{mode}_{i}"] = pos.numpy().astype(np.int32)
-        path = os.path.join(outdir, f"{name}.npz")
-        np.savez_compressed(path, **out)
-        print(name, os.path.getsize(path), {k: v.shape for k, v in out.items() if k.startswith("pos_")})
+        gen_golden.save(name, out)
+        print(" ", {k: v.shape for k, v in out.items() if k.startswith("pos_")})
 
 
 if __name__ == "__main__":

@@ -2,27 +2,19 @@
 """Reference outputs of MergingPress: runs the REAL reference (NVIDIA/kvpress, put on the path by oracle/gen_golden.py's shims, as the
 oracle/gen_golden*.py scripts do) on the host CPU over the seeded inputs of tests/_merging_inputs.py and writes tests/golden/mrg_*.npz.
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_merging.py [case ...]
+    PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden_merging.py [case ...]
 
 Per case and run ("o32": module and tensors in float32; "nat": the case's model dtype): the kept indices in the reference's order
 (descending score, `*_kept`), the nearest survivor and its cosine as the reference's merge() computed them (`*_target`, `*_max_sim`:
 recorded from its `.max(dim=-1)` call while compress() runs) and the compressed V' it returns (`*_v`, float32).
 """
-import os
 import sys
 
-os.environ["PYTHONDONTWRITEBYTECODE"] = "1"
-sys.dont_write_bytecode = True
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tests"))
-sys.path.insert(0, os.path.join(REPO, "oracle"))
-sys.path.insert(0, REPO)
+import gen_golden  # (next to this script) the generators' shared opening and closing
 
 
 def main(argv):
-    from gen_golden import _install_shims
-
-    _install_shims()
+    gen_golden.setup()
     import numpy as np
     import torch
     import kvpress  # the reference
@@ -52,7 +44,6 @@ def main(argv):
         def __exit__(self, *exc):
             torch.Tensor.max = self.orig
 
-    outdir = os.path.join(REPO, "tests", "golden")
     for name in argv or list(MI.CASES):
         s = MI.make_case(name)
         out = {}
@@ -74,9 +65,7 @@ def main(argv):
                 out[f"{run}_max_sim"] = r.seen[0][0].float().numpy()
                 out[f"{run}_target"] = r.seen[0][1].numpy().astype(np.int32)
             out[f"{run}_v"] = v2.float().numpy()
-        path = os.path.join(outdir, name + ".npz")
-        np.savez_compressed(path, **out)
-        print(f"{path}: {os.path.getsize(path)} bytes")
+        gen_golden.save(name, out)
 
 
 if __name__ == "__main__":

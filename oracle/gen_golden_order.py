@@ -17,29 +17,21 @@ Test infrastructure only.  The GPU box only sees the committed tests/golden/orde
 
     PYTHONDONTWRITEBYTECODE=1 python oracle/gen_golden_order.py [case ...]
 """
-import os
 import sys
 
-os.environ["PYTHONDONTWRITEBYTECODE"] = "1"
-sys.dont_write_bytecode = True
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tests"))
-sys.path.insert(0, os.path.join(REPO, "oracle"))
+import gen_golden  # (next to this script) the generators' shared opening and closing
 
 ORDER_CASES = ["kn_readme", "kn_tiny_d6", "kn_d96_bf16", "sk_257_A", "sk_257_B", "sk_f16_d64", "ea_257_A", "ea_nocov"]
 
 
 def main(argv):
-    from gen_golden import _install_shims
-
-    _install_shims()
+    gen_golden.setup()
     import numpy as np
     import torch
     from kvpress import ExpectedAttentionPress, KnormPress, SnapKVPress  # the reference
 
     import _inputs
 
-    outdir = os.path.join(REPO, "tests", "golden")
     for name in argv or ORDER_CASES:
         s = _inputs.make_case(name)
         ratios = tuple(r for r in (0.25, 0.5, 0.8) if int(s["S"] * (1 - r)) >= 1)
@@ -80,10 +72,8 @@ def main(argv):
                 out[f"idx_{i}"] = top.indices.numpy().astype(np.int32)
                 out[f"val_{i}"] = chain.float().numpy()
                 out[f"gap_{i}"] = rel.amin(-1).numpy()
-        path = os.path.join(outdir, f"order_{name}.npz")
-        np.savez_compressed(path, **out)
-        print(f"order_{name}: {os.path.getsize(path)} bytes; min relative gaps per ratio: "
-              f"{[float(out[f'gap_{i}'].min()) for i in range(len(ratios))]}")
+        gen_golden.save(f"order_{name}", out)
+        print(f"  min relative gaps per ratio: {[float(out[f'gap_{i}'].min()) for i in range(len(ratios))]}")
 
 
 # ---- chains (round 6): an order-dependent press behind a ScorerPress -----------------------------------------------------------------
@@ -100,16 +90,13 @@ CHAIN_CASES = {
 
 
 def main_chains():
-    from gen_golden import _install_shims
-
-    _install_shims()
+    gen_golden.setup()
     import numpy as np
     import torch
     import kvpress as K  # the reference
 
     import _inputs
 
-    outdir = os.path.join(REPO, "tests", "golden")
     for cname, (case, r1, (p2name, p2kw)) in CHAIN_CASES.items():
         s = _inputs.make_case(case)
         att, rot, hidden, pe = _inputs.build_llama_attention(s, torch.float32)
@@ -131,9 +118,8 @@ def main_chains():
         for nm, t_ in (("ko", k2), ("vo", v2)):
             assert torch.equal(t_.to(dt).float(), t_)
             out[nm] = t_.numpy().astype(np.float32) if dt == torch.float32 else t_.to(dt).view(torch.int16).numpy().view(np.uint16)
-        path = os.path.join(outdir, f"order_{cname}.npz")
-        np.savez_compressed(path, **out)
-        print(f"order_{cname}: {tuple(k2.shape)}; {os.path.getsize(path)} bytes; min gap at the second threshold {float(np.min(gap)):.3e}")
+        gen_golden.save(f"order_{cname}", out)
+        print(f"  {tuple(k2.shape)}; min gap at the second threshold {float(np.min(gap)):.3e}")
 
 
 if __name__ == "__main__":

@@ -9,18 +9,12 @@ attention layers, which the reference hook reads (base_press.py:145) -- a forwar
 """
 import json
 import os
-import sys
 
-os.environ["PYTHONDONTWRITEBYTECODE"] = "1"
-sys.dont_write_bytecode = True
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tests"))
-sys.path.insert(0, os.path.join(REPO, "oracle"))
+import gen_golden  # (next to this script) the generators' shared opening and closing
 
 
 def main():
-    import gen_golden
-    gen_golden._install_shims()
+    gen_golden.setup()
     import kvpress
     import torch
     from kvpress.pipeline import KVPressTextGenerationPipeline
@@ -71,7 +65,7 @@ def main():
             _inputs.tiny_context(n_words), questions=questions, press=_inputs.build_press(kvpress, spec), max_new_tokens=max_new, cache=cache)
         out[name] = {"answers": res["answers"], "cache_lengths": [int(cache.get_seq_length(i)) for i in range(len(cache))]}
         print(name, out[name])
-    with open(os.path.join(REPO, "tests", "golden", "pipeline.json"), "w") as f:
+    with open(os.path.join(gen_golden.GOLDEN, "pipeline.json"), "w") as f:
         json.dump(out, f, indent=1)
 
 

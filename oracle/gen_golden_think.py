@@ -8,26 +8,19 @@ Per case: qwin_f32 (the RoPE'd window queries of the float32 run) and, per ratio
 pruned_<run>_<i> [B,H,n]: the channels the reference zeroed, ascending (read off its output keys: the inputs have no
 exact zeros).
 """
-import os
 import sys
 
-os.environ["PYTHONDONTWRITEBYTECODE"] = "1"
-sys.dont_write_bytecode = True
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tests"))
-sys.path.insert(0, os.path.join(REPO, "oracle"))
+import gen_golden  # (next to this script) the generators' shared opening and closing
 
 
 def main(argv):
-    import gen_golden
-    gen_golden._install_shims()
+    gen_golden.setup()
     import numpy as np
     import torch
     from kvpress import ThinKPress
 
     import _inputs
 
-    outdir = os.path.join(REPO, "tests", "golden")
     for name in (argv or list(_inputs.THINK_CASES)):
         s = _inputs.make_think_case(name)
         assert not (s["keys"] == 0).any()
@@ -48,9 +41,8 @@ def main(argv):
                     n = int(s["D"] * r)
                     assert (zero.sum(-1) == n).all()
                     out[f"pruned_{mode}_{i}"] = torch.nonzero(zero)[:, 2].view(s["B"], s["H"], n).numpy().astype(np.int32)
-        path = os.path.join(outdir, f"{name}.npz")
-        np.savez_compressed(path, **out)
-        print(name, os.path.getsize(path), {k: v.shape for k, v in out.items() if k.startswith("pruned_")})
+        gen_golden.save(name, out)
+        print(" ", {k: v.shape for k, v in out.items() if k.startswith("pruned_")})
 
 
 if __name__ == "__main__":

@@ -11,10 +11,8 @@ import json
 import os
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [REPO, os.path.join(REPO, "tests"), os.path.join(REPO, "oracle")]
-
-import torch_path_pinned as TPP  # noqa: E402
+import gen_golden  # (next to this script) the generators' shared opening and closing
+import torch_path_pinned as TPP
 
 
 def cases():
@@ -26,9 +24,7 @@ def cases():
 
 def main():
     TPP.pin()
-    import gen_golden
-
-    gen_golden._install_shims()
+    gen_golden.setup()
     import numpy as np
     import torch
     from kvpress import ExpectedAttentionPress, KnormPress, SnapKVPress  # the reference
@@ -60,7 +56,7 @@ def main():
                         n = ko.shape[2]
                         out[TPP.key(name, f"nkept_{i}")] = np.int64(n)
                         out[TPP.key(name, f"idx_f32_{i}")] = sc.topk(n, dim=-1).indices.sort(dim=-1).values.numpy().astype(np.int32)
-    path = os.path.join(REPO, "tests", "golden", "torch_path_pinned.json")
+    path = os.path.join(gen_golden.GOLDEN, "torch_path_pinned.json")
     with open(path, "w") as f:   # one entry per line
         f.write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(v)}" for k, v in TPP.record(out).items()) + "\n}\n")
     print(f"{len(cases())} cases: wrote {os.path.getsize(path)} bytes to {path}")

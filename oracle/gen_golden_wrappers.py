@@ -9,26 +9,19 @@ K and V with the same indices).  Per case and ratio i:  pos_<i> int32 [B,H,n] (s
 the order inside a chunk is torch.topk's), and for the rerotation wrapper  kout_f32_<i> / kout_nat_<i>: the re-rotated
 keys of the float32 run and of the native-dtype run (float32 storage).
 """
-import os
 import sys
 
-os.environ["PYTHONDONTWRITEBYTECODE"] = "1"
-sys.dont_write_bytecode = True
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tests"))
-sys.path.insert(0, os.path.join(REPO, "oracle"))
+import gen_golden  # (next to this script) the generators' shared opening and closing
 
 
 def main(argv):
-    import gen_golden
-    gen_golden._install_shims()
+    gen_golden.setup()
     import numpy as np
     import torch
     from kvpress import AdaKVPress, BlockPress, ChunkKVPress, ChunkPress, CriticalAdaKVPress, CriticalKVPress, KeyDiffPress, KeyRerotationPress, KnormPress, SnapKVPress, StreamingLLMPress
 
     import _inputs
 
-    outdir = os.path.join(REPO, "tests", "golden")
     for name in (argv or list(_inputs.WRAP_CASES)):
         s = _inputs.make_wrap_case(name)
 
@@ -104,9 +97,8 @@ def main(argv):
                         out[f"kout_{mode}_{i}"] = ko.float().numpy()
                         if mode == "nat":
                             out[f"pos_nat_{i}"] = pos.numpy().astype(np.int32)
-        path = os.path.join(outdir, f"{name}.npz")
-        np.savez_compressed(path, **out)
-        print(name, os.path.getsize(path), {k: v.shape for k, v in out.items() if k.startswith(("pos_", "masked_"))})
+        gen_golden.save(name, out)
+        print(" ", {k: v.shape for k, v in out.items() if k.startswith(("pos_", "masked_"))})
 
 
 if __name__ == "__main__":

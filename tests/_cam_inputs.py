@@ -1,4 +1,4 @@
-"""Seeded inputs of the CAMPress fixtures (tests/golden/cam_*.npz, tools/gen_golden_cam.py): the cache of _merging_inputs, an attention
+"""Seeded inputs of the CAMPress fixtures (tests/golden/cam_*.npz, oracle/gen_golden_cam.py): the cache of _merging_inputs, an attention
 layer with q_proj and rotary tables from _inputs.build_llama_attention, and a running attention sum (rounded to the case's dtype, so
 the float32 run and the native run of the reference see the same numbers)."""
 from __future__ import annotations

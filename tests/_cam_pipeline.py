@@ -4,22 +4,8 @@ tests/test_gpu_cam.py (the HIP kernels)."""
 import torch
 
 import _inputs
+from _support import cache_sizes, tiny_pipeline
 from kvpress_amd.utils import extract_keys_and_values
-
-
-def _pipe(device="cpu", dtype=None, eager=False):
-    from transformers import pipeline
-
-    import kvpress_amd  # noqa: F401  (registers the task)
-
-    model = _inputs.make_tiny_llama(dtype=dtype, device=device)
-    if eager:
-        model.config._attn_implementation = "eager"
-    return pipeline("kv-press-text-generation", model=model, tokenizer=_inputs.make_tiny_tokenizer(), device=device)
-
-
-def _sizes(cache):
-    return [layer.keys.shape[2] for layer in cache.layers]
 
 
 def _watched(press, cam):
@@ -46,20 +32,20 @@ def check_cam_pipeline(device, dtype, eager=False):
 
     import kvpress_amd as P
 
-    pipe = _pipe(device, dtype, eager)
+    pipe = tiny_pipeline(device, dtype, eager)
     for target, interval, budget in ((32, 4, 32), (64, 3, 2), (128, 5, 200)):
         press = P.CAMPress(base_press=P.KnormPress(compression_ratio=0.5), compression_interval=interval, target_size=target, merge_budget=budget)
         seen = _watched(press, press)
         cache = DynamicCache()
         res = pipe(_inputs.tiny_context(100 if target < 128 else 140), question="w1 w2 w3", press=press, cache=cache, max_new_tokens=20)
         assert isinstance(res["answer"], str) and seen
-        assert all(target <= n <= target + interval - 1 for n in _sizes(cache)), (target, _sizes(cache))
+        assert all(target <= n <= target + interval - 1 for n in cache_sizes(cache)), (target, cache_sizes(cache))
         assert press._running_attn_sum == {} and press._attn_buffer == {}        # the context manager's exit resets
     # the cache is below the target: steps are counted, nothing is compressed
     press = P.CAMPress(base_press=P.KnormPress(), compression_interval=2, target_size=400)
     cache = DynamicCache()
     pipe(_inputs.tiny_context(50), question="w6", press=press, cache=cache, max_new_tokens=6)
-    assert all(n > 50 for n in _sizes(cache))
+    assert all(n > 50 for n in cache_sizes(cache))
     # a QuantizedCache: the merged keys / values are re-quantised into the layer (DecodingPress's write-back).  As in the reference the
     # press sees the quantised part only, which grows by the residual buffer's 8 tokens at a time.
     press = P.CAMPress(base_press=P.KnormPress(), compression_interval=3, target_size=40, merge_budget=4)
@@ -73,7 +59,7 @@ def check_cam_pipeline(device, dtype, eager=False):
     seen = _watched(combined, cam)
     cache = DynamicCache()
     pipe(_inputs.tiny_context(130), question="w4 w5", press=combined, cache=cache, max_new_tokens=15)
-    assert seen and all(48 <= n <= 48 + 3 - 1 for n in _sizes(cache)), _sizes(cache)
+    assert seen and all(48 <= n <= 48 + 3 - 1 for n in cache_sizes(cache)), cache_sizes(cache)
     assert combined.prefilling_press.kept_order == "score"                     # CAM's windows are neighbours in CACHE order
     # one press object, two sequences of different length: nothing of the first is added to in the second
     press = P.CAMPress(base_press=P.KnormPress(), compression_interval=3, target_size=40, merge_budget=8)
@@ -81,5 +67,5 @@ def check_cam_pipeline(device, dtype, eager=False):
     for n_ctx in (60, 75, 60):
         cache = DynamicCache()
         torch.manual_seed(0)                                                     # the Bernoulli draws
-        outs.append((pipe(_inputs.tiny_context(n_ctx), question="w3", press=press, cache=cache, max_new_tokens=9)["answer"], _sizes(cache)))
+        outs.append((pipe(_inputs.tiny_context(n_ctx), question="w3", press=press, cache=cache, max_new_tokens=9)["answer"], cache_sizes(cache)))
     assert outs[0] == outs[2]

@@ -1,4 +1,4 @@
-"""Seeded inputs of the Compactor-family fixtures (tests/golden/cpt_*.npz, tools/gen_golden_compactor.py): the attention layer of
+"""Seeded inputs of the Compactor-family fixtures (tests/golden/cpt_*.npz, oracle/gen_golden_compactor.py): the attention layer of
 _inputs.build_llama_attention with its k_proj seeded as well (that helper leaves it to torch's init)."""
 from __future__ import annotations
 

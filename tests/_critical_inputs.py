@@ -1,4 +1,4 @@
-"""Seeded inputs of the CriticalKV fixtures (tests/golden/crit_*.npz, tools/gen_golden_critical.py): a cache, hidden states and q_proj
+"""Seeded inputs of the CriticalKV fixtures (tests/golden/crit_*.npz, oracle/gen_golden_critical.py): a cache, hidden states and q_proj
 from _inputs.make_case, and the attention layer of _inputs.build_llama_attention, whose o_proj is seeded there.  Every number is exact
 in the case's 16-bit dtype, so the reference's float32 run and its native run see the same inputs."""
 from __future__ import annotations

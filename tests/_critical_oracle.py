@@ -4,7 +4,7 @@ Test infrastructure only.
 
 Ties.  torch.topk leaves the choice among near-equal scores open and the reference computes in float32, so every selection here also
 reports its BAND: the positions within ``rel`` (1e-3) of that selection's threshold.  Kept sets, masks and filled entries are compared
-outside the union of the bands (sets_equal_outside); tools/gen_golden_critical.py asserts that the bands of the fixtures are small."""
+outside the union of the bands (sets_equal_outside); oracle/gen_golden_critical.py asserts that the bands of the fixtures are small."""
 from __future__ import annotations
 
 import numpy as np

@@ -1,4 +1,4 @@
-"""Seeded inputs of the MergingPress fixtures (tests/golden/mrg_*.npz, tools/gen_golden_merging.py): cache keys / values drawn with
+"""Seeded inputs of the MergingPress fixtures (tests/golden/mrg_*.npz, oracle/gen_golden_merging.py): cache keys / values drawn with
 numpy's frozen RandomState (rounded to the case's dtype, so both runs see the same numbers) and, for SnapKV, the attention layer of
 _inputs.build_llama_attention."""
 from __future__ import annotations

@@ -1,7 +1,6 @@
 """CAMPress without a GPU: the float64 oracle (tests/_cam_oracle.py) against the reference's fixtures (tests/golden/cam_*.npz), the
 press's host logic over oracle-backed stand-ins of its three library calls, the package surface and the C ABI's argument checks."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -10,32 +9,15 @@ import torch
 import _cam_inputs as CI
 import _cam_oracle as O
 import _inputs
-from _cam_pipeline import _pipe, _sizes, check_cam_pipeline
-
-ULP = {"f32": 2.0 ** -23, "f16": 2.0 ** -10, "bf16": 2.0 ** -7}
-DT_NAME = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}
-
-
-def _golden(name):
-    return dict(np.load(os.path.join(os.path.dirname(os.path.abspath(CI.__file__)), "golden", name + ".npz")))
-
-
-def _merged_tol(ref, dt):
-    """tests/test_gpu_merging.py: one unit in the last place of the dtype (float32: a few float32 ulps)"""
-    if dt == "f32":
-        return 64 * ULP[dt] * np.abs(ref) + 1e-7
-    return ULP[dt] * np.maximum(np.abs(ref), 2.0 ** -14) * 1.0001
-
-
-def _ref_tol(ref_v, dt):
-    return _merged_tol(ref_v, dt) + 2e-6 * max(1.0, float(np.abs(ref_v).max(initial=0.0)))
+from _cam_pipeline import check_cam_pipeline
+from _support import cache_sizes, dtype_name, golden, ref_tol, tiny_pipeline
 
 
 # ---- the oracle reproduces the reference ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(CI.CASES))
 def test_oracle_reproduces_the_reference_compress(name):
     """Worst oracle-vs-reference difference of the float32 run over the three fixtures: prob 5.2e-8, V' 4.8e-7 absolute."""
-    s, g = CI.make_case(name), _golden(name)
+    s, g = CI.make_case(name), golden(name)
     mean = -np.linalg.norm(s["keys"].astype(np.float64), axis=-1).mean(1)          # KnormPress, head mean
     M = min(s["steps"], s["S"] - s["T"])
     kept, cand = O.rank(mean, s["T"], M)
@@ -53,7 +35,7 @@ def test_oracle_reproduces_the_reference_compress(name):
         if run == "o32":
             verr = np.abs(o["v"] - g["o32_v"])
             print(f"{name}: V' max abs err {verr.max():.3g}")
-            assert (verr <= _ref_tol(g["o32_v"], dt)).all(), float(verr.max())
+            assert (verr <= ref_tol(g["o32_v"], dt)).all(), float(verr.max())
     if s["zero_head"] is not None:
         assert (prob[:, s["zero_head"]] == 0).all()                                  # 0 / 0 -> NaN -> 0
 
@@ -61,7 +43,7 @@ def test_oracle_reproduces_the_reference_compress(name):
 @pytest.mark.parametrize("name", list(CI.CASES))
 def test_oracle_reproduces_the_reference_step_attention(name):
     """Worst over the fixtures: 1.6e-8 absolute."""
-    s, g = CI.make_case(name), _golden(name)
+    s, g = CI.make_case(name), golden(name)
     module, hidden, kw = CI.module_and_step(s, torch.float32)
     from kvpress_amd.utils import get_prerope_query_states
 
@@ -89,7 +71,7 @@ def fake_cam(fake_native, monkeypatch):
     def cam_attn_accumulate_(q_pre, cos, sin, keys, running, s_prev):
         calls["q"] += 1
         assert q_pre.shape[2] == 1 and cos.shape[-2] == 1 and running.shape[-1] >= keys.shape[2]
-        q = O.rope_last_query(q_pre.float().numpy(), cos.float().numpy(), sin.float().numpy(), DT_NAME[keys.dtype])
+        q = O.rope_last_query(q_pre.float().numpy(), cos.float().numpy(), sin.float().numpy(), dtype_name(keys.dtype))
         return _store(running, s_prev, O.attention_row(q, keys.float().numpy(), keys.shape[1]))
 
     def cam_attn_accumulate_row_(attn_row, running, s_prev):
@@ -107,7 +89,7 @@ def fake_cam(fake_native, monkeypatch):
     def cam_merge_prune(keys, values, running, kept, cand, start, mask, merge_budget):
         calls["prune"] += 1
         o = O.merge_prune(keys.float().numpy(), values.float().numpy(), running.numpy(), kept.numpy(), cand.numpy(), mask.numpy(), merge_budget,
-                          DT_NAME[keys.dtype])
+                          dtype_name(keys.dtype))
         np.testing.assert_array_equal(o["start"], start.numpy())
         return (torch.from_numpy(o["k"]).to(keys.dtype), torch.from_numpy(o["v"]).to(keys.dtype), torch.from_numpy(o["a"].astype(np.float32)))
 
@@ -128,20 +110,20 @@ def test_cam_pipeline_eager_row_cpu(fake_cam):
 
     import kvpress_amd as P
 
-    pipe = _pipe("cpu", None, eager=True)
+    pipe = tiny_pipeline("cpu", None, eager=True)
     press = P.CAMPress(base_press=P.KnormPress(), compression_interval=4, target_size=32)
     cache = DynamicCache()
     pipe(_inputs.tiny_context(60), question="w1 w2", press=press, cache=cache, max_new_tokens=10)
-    assert all(32 <= n <= 35 for n in _sizes(cache))
+    assert all(32 <= n <= 35 for n in cache_sizes(cache))
     assert fake_cam.cam_calls["row"] > 0 and fake_cam.cam_calls["q"] == 0
 
 
 @pytest.mark.parametrize("name", list(CI.CASES))
 def test_compress_replays_the_reference(fake_cam, name):
-    """compress() called the way tools/gen_golden_cam.py calls the reference's, its mask replayed: the reference's kept set, K', V', A'"""
+    """compress() called the way oracle/gen_golden_cam.py calls the reference's, its mask replayed: the reference's kept set, K', V', A'"""
     import kvpress_amd as P
 
-    s, g = CI.make_case(name), _golden(name)
+    s, g = CI.make_case(name), golden(name)
     module, hidden, kw = CI.module_and_step(s, torch.float32)
     keys, values, running = (torch.from_numpy(s[n]) for n in ("keys", "values", "running"))
     k0, v0, r0 = keys.clone(), values.clone(), running.clone()
@@ -161,7 +143,7 @@ def test_compress_replays_the_reference(fake_cam, name):
     np.testing.assert_array_equal(k2.numpy(), g["o32_k"])
     np.testing.assert_array_equal(press._running_attn_sum[0].numpy(), g["o32_a"])
     err = np.abs(v2.numpy() - g["o32_v"])
-    assert (err <= _ref_tol(g["o32_v"], "f32")).all(), float(err.max())
+    assert (err <= ref_tol(g["o32_v"], "f32")).all(), float(err.max())
     # at or below the target: the inputs come back
     press.target_size = s["S"]
     assert press.compress(module, hidden, keys, values, running, kw) == (keys, values)

@@ -8,10 +8,7 @@ import torch
 
 import _compactor_inputs as CI
 import _compactor_oracle as O
-
-
-def _golden(name):
-    return dict(np.load(f"{CI.__file__.rsplit('/', 1)[0]}/golden/{name}.npz"))
+from _support import golden
 
 
 def _o32_inputs(s):
@@ -27,7 +24,7 @@ def _o32_inputs(s):
 
 @pytest.mark.parametrize("name", list(CI.CASES))
 def test_oracle_reproduces_reference_goldens(name):
-    s, g = CI.make_case(name), _golden(name)
+    s, g = CI.make_case(name), golden(name)
     att, hidden, (cos, sin), q, kpre, keys, values = _o32_inputs(s)
     # the reference runs in float32, the oracle in float64: measured <= 9e-6 relative on these cases
     nc = O.ncattn_raw(q, cos.numpy(), sin.numpy(), keys, values, s["chunk"], "f32")
@@ -81,7 +78,7 @@ def oracle_native(monkeypatch):
 def test_compactor_host_logic_matches_reference(name, oracle_native):
     import kvpress_amd as P
 
-    s, g = CI.make_case(name), _golden(name)
+    s, g = CI.make_case(name), golden(name)
     att, hidden, pe, *_ = _o32_inputs(s)
     keys = torch.from_numpy(CI.post_rope_keys(att, hidden, pe).numpy())
     values = torch.from_numpy(s["values"])

@@ -5,19 +5,7 @@ import pytest
 import torch
 
 import _inputs
-
-
-def _pipe(device="cpu", dtype=None):
-    from transformers import pipeline
-
-    import kvpress_amd  # noqa: F401  (registers the task)
-
-    return pipeline("kv-press-text-generation", model=_inputs.make_tiny_llama(dtype=dtype, device=device), tokenizer=_inputs.make_tiny_tokenizer(),
-                    device=device)
-
-
-def _sizes(cache):
-    return [layer.keys.shape[2] for layer in cache.layers]
+from _support import cache_sizes, tiny_pipeline
 
 
 def _check_decoding_compression(device, dtype):
@@ -25,37 +13,37 @@ def _check_decoding_compression(device, dtype):
 
     import kvpress_amd as P
 
-    pipe = _pipe(device, dtype)
+    pipe = tiny_pipeline(device, dtype)
     # test_decoding_compression (:51-83): the cache never exceeds target + interval - 1
     for target in (32, 64, 128):
         press = P.DecodingPress(base_press=P.KnormPress(compression_ratio=0.5), compression_interval=4, target_size=target)
         cache = DynamicCache()
         pipe(_inputs.tiny_context(100), question="w1 w2 w3", press=press, cache=cache, max_new_tokens=20)
-        assert all(n <= target + press.compression_interval - 1 for n in _sizes(cache)), (target, _sizes(cache))
+        assert all(n <= target + press.compression_interval - 1 for n in cache_sizes(cache)), (target, cache_sizes(cache))
     # test_prefill_decoding_press_calls_both_phases (:86-117)
     combined = P.PrefillDecodingPress(prefilling_press=P.KnormPress(compression_ratio=0.6),
                                       decoding_press=P.DecodingPress(base_press=P.KnormPress(), compression_interval=3, target_size=48))
     cache = DynamicCache()
     pipe(_inputs.tiny_context(130), question="w4 w5", press=combined, cache=cache, max_new_tokens=15)
-    assert all(48 <= n <= 48 + 3 - 1 for n in _sizes(cache)), _sizes(cache)
+    assert all(48 <= n <= 48 + 3 - 1 for n in cache_sizes(cache)), cache_sizes(cache)
     # test_decoding_press_without_prefill (:120-148)
     press = P.DecodingPress(base_press=P.KnormPress(compression_ratio=0.4), compression_interval=5, target_size=64)
     cache = DynamicCache()
     pipe(_inputs.tiny_context(90), question="w6", press=press, cache=cache, max_new_tokens=25)
-    assert all(64 <= n <= 64 + 5 - 1 for n in _sizes(cache)), _sizes(cache)
+    assert all(64 <= n <= 64 + 5 - 1 for n in cache_sizes(cache)), cache_sizes(cache)
     # test_prefill_decoding_press_decoding_only (:151-184)
     combined = P.PrefillDecodingPress(prefilling_press=None,
                                       decoding_press=P.DecodingPress(base_press=P.KnormPress(compression_ratio=0.6), compression_interval=4, target_size=56))
     cache = DynamicCache()
     pipe(_inputs.tiny_context(100), question="w7 w8", press=combined, cache=cache, max_new_tokens=12)
-    assert all(56 <= n <= 56 + 4 - 1 for n in _sizes(cache)), _sizes(cache)
+    assert all(56 <= n <= 56 + 4 - 1 for n in cache_sizes(cache)), cache_sizes(cache)
     # test_decoding_press_equivalence (:187-232): standalone == PrefillDecodingPress(decoding only)
     mk = lambda: P.DecodingPress(base_press=P.KnormPress(compression_ratio=0.5), compression_interval=3, target_size=52)
     c1, c2 = DynamicCache(), DynamicCache()
     r1 = pipe(_inputs.tiny_context(80), question="w9", press=mk(), cache=c1, max_new_tokens=10)
     r2 = pipe(_inputs.tiny_context(80), question="w9", press=P.PrefillDecodingPress(prefilling_press=None, decoding_press=mk()), cache=c2,
               max_new_tokens=10)
-    assert _sizes(c1) == _sizes(c2) and r1["answer"] == r2["answer"]
+    assert cache_sizes(c1) == cache_sizes(c2) and r1["answer"] == r2["answer"]
 
 
 def test_decoding_compression_cpu(fake_native):
@@ -75,19 +63,19 @@ def _check_all_scorers_and_reuse(device, dtype):
 
     import kvpress_amd as P
 
-    pipe = _pipe(device, dtype)
+    pipe = tiny_pipeline(device, dtype)
     for base in _scorers(P):
         press = P.DecodingPress(base_press=base, compression_interval=3, target_size=48)
         cache = DynamicCache()
         res = pipe(_inputs.tiny_context(70), question="w1 w2", press=press, cache=cache, max_new_tokens=12)
         assert isinstance(res["answer"], str)
-        assert all(48 <= n <= 48 + 3 - 1 for n in _sizes(cache)), (type(base).__name__, _sizes(cache))
+        assert all(48 <= n <= 48 + 3 - 1 for n in cache_sizes(cache)), (type(base).__name__, cache_sizes(cache))
     # one press object, two sequences: the per-layer buffers and step counters start afresh
     press = P.DecodingPress(base_press=P.KnormPress(), compression_interval=3, target_size=40)
     outs = []
     for _ in range(2):
         cache = DynamicCache()
-        outs.append((pipe(_inputs.tiny_context(60), question="w3", press=press, cache=cache, max_new_tokens=9)["answer"], _sizes(cache)))
+        outs.append((pipe(_inputs.tiny_context(60), question="w3", press=press, cache=cache, max_new_tokens=9)["answer"], cache_sizes(cache)))
     assert outs[0] == outs[1]
 
 

@@ -1,15 +1,14 @@
 """Host logic of the SURVEY §8 f-2 presses (PyramidKV, TOVA, KeyDiff, StreamingLLM, Random) on CPU: the classes run
 through the oracle-backed fakes of conftest.py and are compared with the REAL reference's outputs (tests/golden)."""
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import _inputs
+from _support import golden
 from oracle import kvpress_oracle as O
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 F2 = [n for n, c in _inputs.CASES.items() if c["kind"] in ("pyramid", "tova", "keydiff", "streaming", "cur", "qfilter", "observed", "lagkv")]
 
 
@@ -40,7 +39,7 @@ def make_press(s, ratio):
 @pytest.mark.parametrize("name", F2)
 def test_press_matches_reference_cpu(name, fake_native):
     s = _inputs.make_case(name)
-    g = np.load(os.path.join(GOLD, f"{name}.npz"))
+    g = golden(name)
     att, rot, hidden, pe = _inputs.build_llama_attention(s, torch.float32)
     if s["kind"] == "qfilter":
         att.layer_idx = _inputs.QF_LAYER

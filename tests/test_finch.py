@@ -1,23 +1,18 @@
 """FinchPress against the REAL reference's outputs (tests/golden/finch_*.npz, oracle/gen_golden_finch.py).
 CPU: the oracle restatement and the press's host logic over oracle-backed entry points; GPU (marked): kvp_finch_score
 and the press on the HIP kernels."""
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import _inputs
+from _support import golden
 from oracle import kvpress_oracle as O
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 NAMES = list(_inputs.FINCH_CASES)
 DEV = "cuda:0"
 RTOL = 1e-3  # BASELINE.json north_star: float scores within 1e-3 relative
-
-
-def gold(name):
-    return np.load(os.path.join(GOLD, f"{name}.npz"))
 
 
 def _close(got, want, W, rtol):
@@ -28,7 +23,7 @@ def _close(got, want, W, rtol):
 @pytest.mark.parametrize("name", NAMES)
 def test_oracle_matches_reference(name):
     s = _inputs.make_finch_case(name)
-    g = gold(name)
+    g = golden(name)
     sc = O.finch_score(g["qwin_f32"], s["keys"], s["normalize"])
     _close(sc, g["scores_f32"], s["W"], 2e-4)
     for i, r in enumerate(s["ratios"]):
@@ -60,7 +55,7 @@ def _run_press(s, name, dev, dt):
 
 
 def _check_fp32(s, name, dev, rtol):
-    g = gold(name)
+    g = golden(name)
     sc, out = _run_press(s, name, dev, torch.float32)
     _close(sc, g["scores_f32"], s["W"], rtol)
     for i, r, ko, pos in out:
@@ -115,7 +110,7 @@ def test_finch_kernel_vs_oracle(name):
 
     s = _inputs.make_finch_case(name)
     dt = _inputs.torch_dtype(s["dtype"])
-    q = _inputs.round_to(gold(name)["qwin_f32"], s["dtype"])
+    q = _inputs.round_to(golden(name)["qwin_f32"], s["dtype"])
     want = O.finch_score(q, s["keys"], s["normalize"])
     W = s["W"]
     one, zero = torch.ones((1, W, s["D"]), dtype=dt, device=DEV), torch.zeros((1, W, s["D"]), dtype=dt, device=DEV)
@@ -138,7 +133,7 @@ def test_press_native_dtype_gpu(name):
     """bf16 / f16 model: fp32 scores from the model-dtype queries give a valid top-k of the float32 reference run (a few
     near-ties may swap), and the re-rotated keys follow the reference's per-op rounding."""
     s = _inputs.make_finch_case(name)
-    g = gold(name)
+    g = golden(name)
     sc, out = _run_press(s, name, DEV, _inputs.torch_dtype(s["dtype"]))
     ulp = 2.0 ** (-8 if s["dtype"] == "bf16" else -11)
     for i, r, ko, pos in out:

@@ -1,7 +1,5 @@
 """CAMPress on the GPU: the three kernels against the float64 oracle (tests/_cam_oracle.py) over the smallest shapes that can go wrong, the
 press against the reference's fixtures (tests/golden/cam_*.npz), the hook through the pipeline and one 128k-key step."""
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -10,27 +8,11 @@ import _cam_inputs as CI
 import _cam_oracle as O
 import _inputs
 from _cam_pipeline import check_cam_pipeline
+from _support import golden, merged_tol, ref_tol, torch_dtype
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-TDT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
-ULP = {"f32": 2.0 ** -23, "f16": 2.0 ** -10, "bf16": 2.0 ** -7}
-
-
-def _golden(name):
-    return dict(np.load(os.path.join(os.path.dirname(os.path.abspath(CI.__file__)), "golden", name + ".npz")))
-
-
-def _merged_tol(ref, dt):
-    """tests/test_gpu_merging.py: one unit in the last place of the dtype (float32: a few float32 ulps)"""
-    if dt == "f32":
-        return 64 * ULP[dt] * np.abs(ref) + 1e-7
-    return ULP[dt] * np.maximum(np.abs(ref), 2.0 ** -14) * 1.0001
-
-
-def _ref_tol(ref_v, dt):
-    return _merged_tol(ref_v, dt) + 2e-6 * max(1.0, float(np.abs(ref_v).max(initial=0.0)))
 
 
 def _score_contract(got, want):
@@ -50,9 +32,9 @@ def _step_inputs(B, H, G, S, D, dt, seed, pad_s=5, pad_d=0):
     ang = rs.uniform(0, 6.28, size=(1, 1, D // 2)).astype(np.float32)
     cos = _inputs.round_to(np.concatenate([np.cos(ang), np.cos(ang)], -1), dt)
     sin = _inputs.round_to(np.concatenate([np.sin(ang), np.sin(ang)], -1), dt)
-    big = torch.zeros((B, H, S + 2 * pad_s, D + pad_d), dtype=TDT[dt], device=DEV)
+    big = torch.zeros((B, H, S + 2 * pad_s, D + pad_d), dtype=torch_dtype(dt), device=DEV)
     view = big[:, :, pad_s:pad_s + S, :D]
-    view.copy_(torch.from_numpy(k).to(TDT[dt]))
+    view.copy_(torch.from_numpy(k).to(torch_dtype(dt)))
     return q, cos, sin, k, view
 
 
@@ -73,7 +55,7 @@ def test_attn_accumulate_against_oracle(S, G, D, dt):
     q, cos, sin, k, kview = _step_inputs(B, H, G, S, D, dt, 100 + S + G + D)
     a = O.attention_row(O.rope_last_query(q, cos[0], sin[0], dt), k, H)
     np.testing.assert_allclose(a.sum(-1), 1.0, atol=1e-12)
-    qt, ct, st = (torch.from_numpy(x).to(DEV, TDT[dt]) for x in (q, cos, sin))
+    qt, ct, st = (torch.from_numpy(x).to(DEV, torch_dtype(dt)) for x in (q, cos, sin))
     rs = np.random.RandomState(7)
     prev = rs.gamma(0.5, 1.0, size=(B, H, cap)).astype(np.float32)
     worst = 0.0
@@ -102,7 +84,7 @@ def test_attn_accumulate_unaligned_rows_take_the_generic_path():
     q, cos, sin, k, kview = _step_inputs(B, H, G, S, D, dt, 5, pad_d=4)
     assert kview.stride(2) == 68
     running = torch.full((B, H, S), float("nan"), device=DEV)
-    _native.cam_attn_accumulate_(*(torch.from_numpy(x).to(DEV, TDT[dt]) for x in (q, cos, sin)), kview, running, 0)
+    _native.cam_attn_accumulate_(*(torch.from_numpy(x).to(DEV, torch_dtype(dt)) for x in (q, cos, sin)), kview, running, 0)
     _score_contract(running.cpu().numpy(), O.attention_row(O.rope_last_query(q, cos[0], sin[0], dt), k, H))
 
 
@@ -112,13 +94,13 @@ def test_running_sum_after_n_steps():
 
     B, H, G, D, dt, S0, n = 2, 2, 4, 128, "bf16", 300, 4
     q, cos, sin, k, _ = _step_inputs(B, H, G, S0 + n, D, dt, 11)
-    keys = torch.from_numpy(k).to(DEV, TDT[dt])
+    keys = torch.from_numpy(k).to(DEV, torch_dtype(dt))
     running = torch.full((B, H, 512), float("nan"), device=DEV)
     want = np.zeros((B, H, S0 + n))
     for i in range(n):
         S = S0 + i + 1
         qi = _inputs.round_to(q * (1 + 0.1 * i), dt)
-        _native.cam_attn_accumulate_(*(torch.from_numpy(x).to(DEV, TDT[dt]) for x in (qi, cos, sin)), keys[:, :, :S], running, S - 1 if i else 0)
+        _native.cam_attn_accumulate_(*(torch.from_numpy(x).to(DEV, torch_dtype(dt)) for x in (qi, cos, sin)), keys[:, :, :S], running, S - 1 if i else 0)
         want[..., :S] += O.attention_row(O.rope_last_query(qi, cos[0], sin[0], dt), k[:, :, :S], H)
     got = running.cpu().numpy()[..., :S0 + n]
     np.testing.assert_allclose(got.sum(-1, dtype=np.float64), float(n), atol=1e-4)
@@ -134,7 +116,7 @@ def test_attn_accumulate_row_mode(S, G, dt):
     rs = np.random.RandomState(S + G)
     w = rs.gamma(0.3, 1.0, size=(B, H * G, Q, S))
     w = _inputs.round_to((w / w.sum(-1, keepdims=True)).astype(np.float32), dt)
-    attn = torch.from_numpy(w).to(DEV, TDT[dt])
+    attn = torch.from_numpy(w).to(DEV, torch_dtype(dt))
     prev = rs.gamma(0.5, 1.0, size=(B, H, S + 9)).astype(np.float32)
     for s_prev in sorted({0, max(S - 1, 0), max(S - 3, 0)}):
         running = torch.from_numpy(prev).to(DEV)
@@ -227,11 +209,11 @@ def test_merge_prune_against_oracle(S, T, M, m, layout, D, dt, mk):
     a, run = _running(B, H, S, 4)
     mask = {"rand": (rs.uniform(size=(B, H, M)) < 0.5), "ones": np.ones((B, H, M)), "zeros": np.zeros((B, H, M)),
             "frac": rs.uniform(size=(B, H, M))}[mk].astype(np.float32)
-    big_k = torch.zeros((B, H, S + 10, D), dtype=TDT[dt], device=DEV)      # strided cache views
+    big_k = torch.zeros((B, H, S + 10, D), dtype=torch_dtype(dt), device=DEV)      # strided cache views
     big_v = torch.zeros_like(big_k)
     keys, values = big_k[:, :, 4:4 + S], big_v[:, :, 4:4 + S]
-    keys.copy_(torch.from_numpy(k).to(TDT[dt]))
-    values.copy_(torch.from_numpy(v).to(TDT[dt]))
+    keys.copy_(torch.from_numpy(k).to(torch_dtype(dt)))
+    values.copy_(torch.from_numpy(v).to(torch_dtype(dt)))
     k0, v0, r0 = big_k.clone(), big_v.clone(), run.clone()
     kt, ct, mt = torch.from_numpy(kept).to(DEV), torch.from_numpy(cand).to(DEV), torch.from_numpy(mask).to(DEV)
     _, start, _ = _native.cam_merge_plan(kt, ct, run, S, m)
@@ -247,7 +229,7 @@ def test_merge_prune_against_oracle(S, T, M, m, layout, D, dt, mk):
     np.testing.assert_array_equal(got[~o["merged"]], o["v"][~o["merged"]])                                # bit-exact without contributors
     ref = o["v"][o["merged"]]
     err = np.abs(got[o["merged"]] - ref)
-    assert (err <= _merged_tol(ref, dt)).all(), float(err.max(initial=0.0))
+    assert (err <= merged_tol(ref, dt)).all(), float(err.max(initial=0.0))
     if layout == "after" or mk == "zeros":
         assert not o["merged"].any()
     if layout == "between":
@@ -257,10 +239,10 @@ def test_merge_prune_against_oracle(S, T, M, m, layout, D, dt, mk):
 # ---- against the reference ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(CI.CASES))
 def test_compress_against_reference_fixtures(name):
-    """the whole compress() on the float32 module with the reference's mask replayed: its kept set (K', A') exactly, its V' to _ref_tol"""
+    """the whole compress() on the float32 module with the reference's mask replayed: its kept set (K', A') exactly, its V' to ref_tol"""
     import kvpress_amd as P
 
-    s, g = CI.make_case(name), _golden(name)
+    s, g = CI.make_case(name), golden(name)
     module, hidden, kw = CI.module_and_step(s, torch.float32, DEV)
     keys, values, running = (torch.from_numpy(s[n]).to(DEV) for n in ("keys", "values", "running"))
     k0, v0 = keys.clone(), values.clone()
@@ -281,7 +263,7 @@ def test_compress_against_reference_fixtures(name):
     np.testing.assert_array_equal(press._running_attn_sum[0].cpu().numpy(), g["o32_a"])
     assert (np.abs(probs[0].cpu().numpy() - g["o32_prob"]) <= 1e-3 * g["o32_prob"] + 1e-6).all()
     err = np.abs(v2.cpu().numpy() - g["o32_v"])
-    assert (err <= _ref_tol(g["o32_v"], "f32")).all(), float(err.max())
+    assert (err <= ref_tol(g["o32_v"], "f32")).all(), float(err.max())
 
 
 @pytest.mark.parametrize("name", list(CI.CASES))
@@ -290,9 +272,9 @@ def test_kernels_against_native_dtype_fixtures(name):
     bits (its merged rows round every product and every scatter_add_ step to the dtype: DESIGN.md section 2, deviation 2)"""
     from kvpress_amd import _native
 
-    s, g = CI.make_case(name), _golden(name)
+    s, g = CI.make_case(name), golden(name)
     dt = s["dtype"]
-    keys, values = (torch.from_numpy(s[n]).to(DEV, TDT[dt]) for n in ("keys", "values"))
+    keys, values = (torch.from_numpy(s[n]).to(DEV, torch_dtype(dt)) for n in ("keys", "values"))
     running = torch.from_numpy(s["running"]).to(DEV)
     kt, ct, mt = (torch.from_numpy(g[f"nat_{n}"]).to(DEV) for n in ("kept", "cand", "mask"))
     _, start, _ = _native.cam_merge_plan(kt, ct, running, s["S"], s["m"])
@@ -309,7 +291,7 @@ def test_step_attention_against_reference_fixtures(name):
     from kvpress_amd import _native
     from kvpress_amd.utils import get_prerope_query_states
 
-    s, g = CI.make_case(name), _golden(name)
+    s, g = CI.make_case(name), golden(name)
     module, hidden, kw = CI.module_and_step(s, torch.float32, DEV)
     keys = torch.from_numpy(s["keys"]).to(DEV)
     cos, sin = kw["position_embeddings"]

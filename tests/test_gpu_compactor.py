@@ -10,6 +10,7 @@ import torch
 import _compactor_inputs as CI
 import _compactor_oracle as O
 from _inputs import round_to, torch_dtype
+from _support import golden
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -117,7 +118,7 @@ def test_compactor_compress_vs_reference_o32(name):
     noise, kept sets equal up to ties (the sink pads tie with the argmax in the reference itself)."""
     import kvpress_amd as P
 
-    s, g = CI.make_case(name), dict(np.load(os.path.join(os.path.dirname(CI.__file__), "golden", name + ".npz")))
+    s, g = CI.make_case(name), golden(name)
     att, hidden, pe = CI.build_attention(s, torch.float32, DEV)
     keys = CI.post_rope_keys(att, hidden, pe)
     values = torch.from_numpy(s["values"]).to(DEV)
@@ -147,7 +148,7 @@ def test_noncausal_native_dtype_vs_reference(name):
     """the native-dtype (bf16) module: the reference's own z-scores of NonCausalAttnPress"""
     import kvpress_amd as P
 
-    s, g = CI.make_case(name), dict(np.load(os.path.join(os.path.dirname(CI.__file__), "golden", name + ".npz")))
+    s, g = CI.make_case(name), golden(name)
     dt = torch_dtype(s["dtype"])
     att, hidden, pe = CI.build_attention(s, dt, DEV)
     keys = CI.post_rope_keys(att, hidden, pe)

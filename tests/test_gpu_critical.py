@@ -8,12 +8,12 @@ import torch
 import _critical_inputs as CI
 import _critical_oracle as CO
 import _inputs
-from test_critical_host import run_presses_against_fixture
+from _critical_checks import run_presses_against_fixture, run_stage1_truncation
+from _support import torch_dtype
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 FMAX = float(np.finfo(np.float32).max)
-DT = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
 
 
 def make_inputs(S, D, hidden, G, Hkv, B, dtype, seed):
@@ -76,7 +76,7 @@ def test_vwl1norm_kernel_against_float64(S, D, hidden, G, Hkv, B, dtype, mode):
     ref = CO.vwl1norm(v, wo, Hkv * G)
     if mode != "norm":
         ref = (sc.astype(np.float64) + np.float64(np.float32(1e-4))) * ref
-    got = run_kernel(torch.from_numpy(v).to(DEV, DT[dtype]), torch.from_numpy(wo).to(DEV, DT[dtype]), torch.from_numpy(sc).to(DEV), Hkv * G, mode)
+    got = run_kernel(torch.from_numpy(v).to(DEV, torch_dtype(dtype)), torch.from_numpy(wo).to(DEV, torch_dtype(dtype)), torch.from_numpy(sc).to(DEV), Hkv * G, mode)
     assert got.dtype == torch.float32 and tuple(got.shape) == (B, Hkv, S)
     got = got.cpu().numpy().astype(np.float64)
     ok = np.abs(sc + 1e-4) > 1e-3 if mode != "norm" else np.ones(ref.shape, bool)   # (away from the cancellation of scores + eps)
@@ -92,11 +92,11 @@ def test_strided_inputs_give_the_same_bits(dtype, D):
 
     S, hidden, G, Hkv, B = 300, 320, 4, 2, 2
     v, wo, _ = make_inputs(S, D, hidden, G, Hkv, B, dtype, seed=7)
-    big = torch.zeros(B, Hkv, S + 24, D + 8, dtype=DT[dtype], device=DEV)
-    big[:, :, 8:8 + S, :D] = torch.from_numpy(v).to(DEV, DT[dtype])
+    big = torch.zeros(B, Hkv, S + 24, D + 8, dtype=torch_dtype(dtype), device=DEV)
+    big[:, :, 8:8 + S, :D] = torch.from_numpy(v).to(DEV, torch_dtype(dtype))
     vs = big[:, :, 8:8 + S, :D]
-    wbig = torch.zeros(hidden, Hkv * G * D + 64, dtype=DT[dtype], device=DEV)
-    wbig[:, :Hkv * G * D] = torch.from_numpy(wo).to(DEV, DT[dtype])
+    wbig = torch.zeros(hidden, Hkv * G * D + 64, dtype=torch_dtype(dtype), device=DEV)
+    wbig[:, :Hkv * G * D] = torch.from_numpy(wo).to(DEV, torch_dtype(dtype))
     ws = wbig[:, :Hkv * G * D]
     assert not vs.is_contiguous() and not ws.is_contiguous()
     ref = _native.vwl1norm(vs.contiguous(), ws.contiguous(), Hkv * G)
@@ -115,7 +115,7 @@ def test_zero_value_row(dtype, D):
     v[0, 1, 7] = 0.0
     sc[0, 1, 7] = sc[0, 0, 9] = FMAX
     norm_ref = CO.vwl1norm(v, wo, Hkv * G)
-    vt, wt = torch.from_numpy(v).to(DEV, DT[dtype]), torch.from_numpy(wo).to(DEV, DT[dtype])
+    vt, wt = torch.from_numpy(v).to(DEV, torch_dtype(dtype)), torch.from_numpy(wo).to(DEV, torch_dtype(dtype))
     norm = _native.vwl1norm(vt, wt, Hkv * G).cpu().numpy()
     assert norm[0, 1, 7] == 0.0 and (np.delete(norm.ravel(), S + 7) > 0).all()
     out = _native.vwl1norm_rescale_(torch.from_numpy(sc).to(DEV), vt, wt, Hkv * G, 1e-4).cpu().numpy()
@@ -166,7 +166,7 @@ def test_native_16bit_module_against_oracle(name):
     from kvpress_amd.presses.criticalkv_press import CriticalKVPress
 
     s = CI.make_case(name)
-    dt = DT[s["dtype"]]
+    dt = torch_dtype(s["dtype"])
     att, _, hidden, pe = _inputs.build_llama_attention(s, dt, DEV)
     att.config._attn_implementation = "sdpa"
     keys, values = torch.from_numpy(s["keys"]).to(DEV, dt), torch.from_numpy(s["values"]).to(DEV, dt)
@@ -209,8 +209,6 @@ def test_native_16bit_module_against_oracle(name):
 
 
 def test_stage1_budgets_are_truncated_from_a_float32_product_gpu(monkeypatch):
-    from test_critical_host import run_stage1_truncation
-
     run_stage1_truncation(DEV, monkeypatch)
 
 

@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 import torch
 
+from _support import golden_path
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 H_Q, H_KV, D, HIDDEN = 32, 8, 128, 4096
@@ -63,14 +65,12 @@ def llama_module():
 
 def full_case(name):
     """CPU-seeded full-size inputs (tests/_fullsize.py) on the GPU + the reference fixture."""
-    import os
-
     import _fullsize as F
 
     spec = F.FULL_CASES[name]
     keys, values = (t.to(DEV) for t in F.make_kv(spec))
     hidden = F.make_hidden(spec).to(DEV)
-    fx = np.load(os.path.join(os.path.dirname(__file__), "golden", f"{name}.npz"))
+    fx = np.load(golden_path(f"{name}.npz"))
     return spec, keys, values, hidden, fx
 
 
@@ -193,14 +193,12 @@ def test_config5_shards_keep_what_the_batched_reference_keeps():
     over the whole batch + 1, snapkv_press.py:103).  (a) every element on its own, as a shard of `bench.py --gpus N` sees it (pad = its own
     maximum + 1), and (b) the whole batch in one call (pad = the batch maximum + 1, the reference's value): scores within 1e-3 of the
     reference's, retained sets the reference's up to the tolerance band, and (a) == (b) up to float32 summation order."""
-    import os
-
     import _fullsize as F
     import kvpress_amd as P
 
     name = "full_snapkv128k_B2"
     spec = F.BATCH_CASES[name]
-    fxa = np.load(os.path.join(os.path.dirname(__file__), "golden", f"{name}.npz"))
+    fxa = np.load(golden_path(f"{name}.npz"))
     S, Bn = spec["S"], len(spec["elements"])
     n = int(S * 0.5)
     kv = [F.make_kv(F.element_spec(spec, b)) for b in range(Bn)]

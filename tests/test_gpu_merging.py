@@ -7,16 +7,11 @@ import torch
 import _inputs
 import _merging_inputs as MI
 import _merging_oracle as O
+from _support import golden, kept_positions, merged_tol, ref_tol, torch_dtype
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-TDT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
-ULP = {"f32": 2.0 ** -23, "f16": 2.0 ** -10, "bf16": 2.0 ** -7}
-
-
-def _golden(name):
-    return dict(np.load(f"{MI.__file__.rsplit('/', 1)[0]}/golden/{name}.npz"))
 
 
 def _run_kernel(keys, values, kept, thr, frac):
@@ -31,13 +26,6 @@ def _run_kernel(keys, values, kept, thr, frac):
     _native.merge_values_(keys, values, kept, k_out, v_out, thr, frac, target=tg, max_sim=ms)
     torch.cuda.synchronize()
     return k_out, v_out, tg, ms
-
-
-def _merged_tol(ref, dt):
-    """one unit in the last place of the dtype (a float32 model: a few float32 ulps, the sums run in float32 vs float64)"""
-    if dt == "f32":
-        return 64 * ULP[dt] * np.abs(ref) + 1e-7
-    return ULP[dt] * np.maximum(np.abs(ref), 2.0 ** -14) * 1.0001
 
 
 def _check_against_oracle(keys_np, values_np, kept_np, thr, frac, dt, k_out, v_out, tg, ms):
@@ -65,7 +53,7 @@ def _check_against_oracle(keys_np, values_np, kept_np, thr, frac, dt, k_out, v_o
     np.testing.assert_array_equal(got[untouched], base[untouched])             # rows without contributions are bit-exact
     ref = o["v"][o["merged"]]
     err = np.abs(got[o["merged"]] - ref)
-    assert (err <= _merged_tol(ref, dt)).all(), float(err.max())
+    assert (err <= merged_tol(ref, dt)).all(), float(err.max())
     return o
 
 
@@ -93,8 +81,8 @@ for i, (B, H, S, D, dt) in enumerate([(1, 1, 1, 64, "bf16"), (1, 8, 2, 128, "bf1
 def test_kernel_against_oracle(B, H, S, D, dt, ratio, thr, frac, seed):
     k, v, kept = _rand_case(B, H, S, D, dt, ratio, seed)
     n = kept.shape[-1]
-    keys = torch.from_numpy(k).to(DEV, TDT[dt])
-    values = torch.from_numpy(v).to(DEV, TDT[dt])
+    keys = torch.from_numpy(k).to(DEV, torch_dtype(dt))
+    values = torch.from_numpy(v).to(DEV, torch_dtype(dt))
     kept_t = torch.from_numpy(kept).to(DEV)
     k0, v0 = keys.clone(), values.clone()
     k_out, v_out, tg, ms = _run_kernel(keys, values, kept_t, thr, frac)
@@ -116,18 +104,12 @@ def test_strided_cache_views():
     _check_against_oracle(k, v, kept, 0.0, 1.0, "bf16", *out)
 
 
-def _ref_tol(ref_v, dt):
-    # the reference's V' up to one unit in the last place of the dtype (its float32 cosines and sums run in another order: where
-    # v' + sum(w v) cancels, that leaves a few 1e-7 absolute)
-    return _merged_tol(ref_v, dt) + 2e-6 * max(1.0, float(np.abs(ref_v).max(initial=0.0)))
-
-
 @pytest.mark.parametrize("run", ["o32", "nat"])
 @pytest.mark.parametrize("name", list(MI.CASES))
 def test_merge_against_reference_fixtures(name, run):
     """the kernel on the reference's own kept indices (its descending-score order) gives the reference's targets and V'"""
-    s, g = MI.make_case(name), _golden(name)
-    tdt = torch.float32 if run == "o32" else TDT[s["dtype"]]
+    s, g = MI.make_case(name), golden(name)
+    tdt = torch.float32 if run == "o32" else torch_dtype(s["dtype"])
     dt = "f32" if run == "o32" else s["dtype"]
     kept = g[f"{run}_kept"]
     keys = torch.from_numpy(s["keys"]).to(DEV, tdt)
@@ -144,7 +126,7 @@ def test_merge_against_reference_fixtures(name, run):
         np.testing.assert_allclose(ms.cpu().numpy(), g[f"{run}_max_sim"], atol=1e-5)
     ref_v = g[f"{run}_v"]
     err = np.abs(v_out.float().cpu().numpy() - ref_v)
-    assert (err <= _ref_tol(ref_v, dt)).all(), float(err.max(initial=0.0))
+    assert (err <= ref_tol(ref_v, dt)).all(), float(err.max(initial=0.0))
 
 
 @pytest.mark.parametrize("order", ["position", "score"])
@@ -155,8 +137,8 @@ def test_press_against_reference_fixtures(name, order):
     run = "o32"
     import kvpress_amd as P
 
-    s, g = MI.make_case(name), _golden(name)
-    tdt = torch.float32 if run == "o32" else TDT[s["dtype"]]
+    s, g = MI.make_case(name), golden(name)
+    tdt = torch.float32 if run == "o32" else torch_dtype(s["dtype"])
     dt = "f32" if run == "o32" else s["dtype"]
     module, hidden, kw = MI.module_and_kwargs(s, tdt, DEV)
     keys = torch.from_numpy(s["keys"]).to(DEV, tdt)
@@ -178,28 +160,17 @@ def test_press_against_reference_fixtures(name, order):
         kept = np.take_along_axis(kept, perm, -1)
         ref_v = np.take_along_axis(ref_v, perm[..., None].repeat(D, -1), 2)
         if order == "score":
-            mine = np.argsort(_kept_positions(got_k, s["keys"]), axis=-1, kind="stable")
+            mine = np.argsort(kept_positions(got_k, s["keys"]), axis=-1, kind="stable")
             got_k = np.take_along_axis(got_k, mine[..., None].repeat(D, -1), 2)
             got = np.take_along_axis(got, mine[..., None].repeat(D, -1), 2)
     assert got.shape == ref_v.shape
     np.testing.assert_array_equal(got_k, np.take_along_axis(s["keys"], kept.astype(np.int64)[..., None].repeat(D, -1), 2))
     err = np.abs(got - ref_v)
-    assert (err <= _ref_tol(ref_v, dt)).all(), float(err.max(initial=0.0))
-
-
-def _kept_positions(k_out, keys):
-    """the cache position of every row of K' (the keys of these cases are distinct rows)"""
-    B, H, n, D = k_out.shape
-    pos = np.zeros((B, H, n), np.int64)
-    for b in range(B):
-        for h in range(H):
-            lut = {keys[b, h, s].tobytes(): s for s in range(keys.shape[2])}
-            pos[b, h] = [lut[r.tobytes()] for r in k_out[b, h]]
-    return pos
+    assert (err <= ref_tol(ref_v, dt)).all(), float(err.max(initial=0.0))
 
 
 def test_duplicate_keys_tie_to_the_lowest_kept_index():
-    s, g = MI.make_case("mrg_knorm_dup_s96_d64"), _golden("mrg_knorm_dup_s96_d64")
+    s, g = MI.make_case("mrg_knorm_dup_s96_d64"), golden("mrg_knorm_dup_s96_d64")
     keys = torch.from_numpy(s["keys"]).to(DEV, torch.bfloat16)
     values = torch.from_numpy(s["values"]).to(DEV, torch.bfloat16)
     for kept in (g["o32_kept"], np.ascontiguousarray(np.sort(g["o32_kept"], axis=-1))):
@@ -213,7 +184,7 @@ def test_duplicate_keys_tie_to_the_lowest_kept_index():
 
 
 def test_nan_quantile_row_merges_nothing():
-    s, g = MI.make_case("mrg_knorm_nanq_s200_d128"), _golden("mrg_knorm_nanq_s200_d128")
+    s, g = MI.make_case("mrg_knorm_nanq_s200_d128"), golden("mrg_knorm_nanq_s200_d128")
     kept = g["nat_kept"]
     keys = torch.from_numpy(s["keys"]).to(DEV, torch.bfloat16)
     values = torch.from_numpy(s["values"]).to(DEV, torch.bfloat16)

@@ -8,28 +8,23 @@ Contract:
     tie-tolerant set validity when the scores come from different float32 pipelines;
   * gather: bit-exact.
 """
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import _inputs
+from _support import golden
 from oracle import kvpress_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 DEV = "cuda:0"
 RTOL = 1e-3  # north_star tolerance on float scores
 
 KN = [n for n, c in _inputs.CASES.items() if c["kind"] == "knorm"]
 SK = [n for n, c in _inputs.CASES.items() if c["kind"] == "snapkv"]
 EA = [n for n, c in _inputs.CASES.items() if c["kind"] == "ea"]
-
-
-def gold(name):
-    return np.load(os.path.join(GOLD, f"{name}.npz"))
 
 
 def to_dev(x, dtype_name):
@@ -82,7 +77,7 @@ def test_rownorm_strided_views():
 def test_topk_bitexact_on_reference_scores(name):
     """Same float32 scores (the reference's own O32 scores) into oracle and kernel: identical indices."""
     s = _inputs.spec(name)
-    g = gold(name)
+    g = golden(name)
     ref = g["scores_f32"]
     sc = torch.from_numpy(ref).to(DEV)
     for i, r in enumerate(s["ratios"]):
@@ -100,7 +95,7 @@ def test_topk_order_score_matches_torch_topk(name):
     """KVP_ORDER_SCORE: descending score, ties by ascending position -- on the reference's own float32 scores the kernel
     returns the oracle's order, which is torch.topk(sorted=True)'s wherever the scores are distinct."""
     s = _inputs.spec(name)
-    g = gold(name)
+    g = golden(name)
     ref = g["scores_f32"]
     sc = torch.from_numpy(ref).to(DEV)
     N = native()
@@ -286,7 +281,7 @@ def test_gather_bitexact(name):
 def test_snapkv_kernel_vs_oracle(name):
     """Identical RoPE'd window queries (rounded to the case dtype) into oracle and kernel."""
     s = _inputs.make_case(name)
-    g = gold(name)
+    g = golden(name)
     q = _inputs.round_to(g["qwin_f32"], s["dtype"])
     want = O.snapkv_score(q, s["keys"], s["ks"])
     got = native().snapkv_score(to_dev(q, s["dtype"]), to_dev(s["keys"], s["dtype"]), s["ks"]).cpu().numpy()
@@ -347,7 +342,7 @@ def test_snapkv_kernel_many_chunks(S, Hq):
 @pytest.mark.parametrize("name", ["sk_tiny", "sk_257_A", "sk_f16_d64"])
 def test_snapkv_from_attentions(name):
     s = _inputs.make_case(name)
-    g = gold(name)
+    g = golden(name)
     q = _inputs.round_to(g["qwin_f32"], s["dtype"])
     wa = O.snapkv_window_attention(q, s["keys"])                  # [B,Hq,W,S-W]
     S, W = s["S"], s["W"]
@@ -611,7 +606,7 @@ def test_press_fp32_vs_reference(name):
     """Module and tensors in float32 (= the reference's O32 run): scores within 1e-3, compress()
     output shape and dtype as the reference, retained set a valid top-k of the reference scores."""
     s = _inputs.make_case(name)
-    g = gold(name)
+    g = golden(name)
     att, rot, hidden, pe = _inputs.build_llama_attention(s, torch.float32, DEV)
     if s["kind"] == "qfilter":
         att.layer_idx = _inputs.QF_LAYER
@@ -670,7 +665,7 @@ def test_press_native_dtype_runs_and_overlaps_reference(name):
     Knorm is exact up to ties; the others agree with the reference outside a few-ulp band around its threshold and overlap
     its own top-k to within 2 % of what the float32-mode reference itself achieves."""
     s = _inputs.make_case(name)
-    g = gold(name)
+    g = golden(name)
     dt = _inputs.torch_dtype(s["dtype"])
     att, rot, hidden, pe = _inputs.build_llama_attention(s, dt, DEV)
     if s["kind"] == "qfilter":

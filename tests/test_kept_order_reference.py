@@ -8,15 +8,14 @@ an implementation's float32 score error the order is not defined either.  So the
 larger than the scorer's margin; inside a run the SET of rows must match, and every run of length one -- the general case --
 must match the reference's tensor rows bit for bit.  Cases whose every gap exceeds the margin are compared with torch.equal on the
 whole tensor.  The GPU test runs the kernels; the CPU test runs the same check through the oracle-backed stand-in (host logic)."""
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import _inputs
+from _support import golden
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 ORDER_CASES = ["kn_readme", "kn_tiny_d6", "kn_d96_bf16", "sk_257_A", "sk_257_B", "sk_f16_d64", "ea_257_A", "ea_nocov"]
 # relative score margin below which the order of two neighbours is not considered defined (>= 4 x the measured kernel-vs-reference
 # float32 score error of DESIGN.md §2: Knorm / SnapKV ~4e-7, ExpectedAttention < 1e-4)
@@ -51,7 +50,7 @@ def check_case(name, device, native, force_f32=False):
 
     s = _inputs.make_case(name)
     dt = torch.float32 if force_f32 else _inputs.torch_dtype(s["dtype"])   # (the numpy stand-in of the host test has no bf16)
-    fx = np.load(os.path.join(GOLD, f"order_{name}.npz"))
+    fx = golden(f"order_{name}")
     att, rot, hidden, pe = _inputs.build_llama_attention(s, dt, device)
     keys = torch.from_numpy(s["keys"]).to(device=device, dtype=dt)
     values = torch.from_numpy(s["values"]).to(device=device, dtype=dt)
@@ -142,7 +141,7 @@ def check_chain(cname, device, explicit_position=False):
 
     case, r1, mk2 = CHAINS[cname]
     s = _inputs.make_case(case)
-    fx = np.load(os.path.join(GOLD, f"order_{cname}.npz"))
+    fx = golden(f"order_{cname}")
     dt = torch.float32
     att, rot, hidden, pe = _inputs.build_llama_attention(s, dt, device)
     keys = torch.from_numpy(s["keys"]).to(device=device, dtype=dt)

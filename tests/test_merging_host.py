@@ -9,10 +9,7 @@ import torch
 import _inputs
 import _merging_inputs as MI
 import _merging_oracle as O
-
-
-def _golden(name):
-    return dict(np.load(f"{MI.__file__.rsplit('/', 1)[0]}/golden/{name}.npz"))
+from _support import dtype_name, golden, kept_positions
 
 
 def _nat_inputs(s, run):
@@ -23,7 +20,7 @@ def _nat_inputs(s, run):
 @pytest.mark.parametrize("run", ["o32", "nat"])
 @pytest.mark.parametrize("name", list(MI.CASES))
 def test_oracle_reproduces_reference_goldens(name, run):
-    s, g = MI.make_case(name), _golden(name)
+    s, g = MI.make_case(name), golden(name)
     keys, values = _nat_inputs(s, run)
     kept = g[f"{run}_kept"]
     dt = "f32" if run == "o32" else s["dtype"]
@@ -46,13 +43,13 @@ def test_oracle_reproduces_reference_goldens(name, run):
 
 def test_fixtures_cover_the_edge_cases():
     """the NaN-quantile row merges nothing, the duplicate keys tie, n_kept == 0 returns empty tensors"""
-    s, g = MI.make_case("mrg_knorm_nanq_s200_d128"), _golden("mrg_knorm_nanq_s200_d128")
+    s, g = MI.make_case("mrg_knorm_nanq_s200_d128"), golden("mrg_knorm_nanq_s200_d128")
     o = O.merge(s["keys"], s["values"], g["o32_kept"], s["thr"], s["frac"], "f32")
     assert o["merged"][0, 0].any() and not o["merged"][0, 1].any()
     masked = np.where(o["max_sim"] >= np.float32(s["thr"]), o["max_sim"], -np.inf)
     assert np.isnan(O.aten_quantile(masked, 1 - s["frac"])[0, 1])
     np.testing.assert_array_equal(g["o32_v"][0, 1], np.take_along_axis(s["values"][0, 1], g["o32_kept"][0, 1][:, None].astype(np.int64), 0))
-    s, g = MI.make_case("mrg_knorm_dup_s96_d64"), _golden("mrg_knorm_dup_s96_d64")
+    s, g = MI.make_case("mrg_knorm_dup_s96_d64"), golden("mrg_knorm_dup_s96_d64")
     ev = O.evicted_positions(g["o32_kept"], s["S"])
     ties = 0
     for h in range(s["H"]):
@@ -61,7 +58,7 @@ def test_fixtures_cover_the_edge_cases():
         ties += int(((sim >= best - 1e-12).sum(-1) > 1).sum())
         np.testing.assert_array_equal(g["o32_target"][0, h], sim.argmax(-1))   # the lowest index among the tied
     assert ties > 0
-    g = _golden("mrg_knorm_nkept0_s20_d64")
+    g = golden("mrg_knorm_nkept0_s20_d64")
     assert g["o32_v"].shape[2] == 0 and g["o32_kept"].shape[2] == 0
 
 
@@ -106,17 +103,6 @@ def test_post_init_from_model_forwards():
     assert seen == ["m"]
 
 
-def _kept_positions(k_out, keys):
-    """the cache position of every row of K' (the keys of these cases are distinct rows)"""
-    B, H, n, D = k_out.shape
-    pos = np.zeros((B, H, n), np.int64)
-    for b in range(B):
-        for h in range(H):
-            lut = {keys[b, h, s].tobytes(): s for s in range(keys.shape[2])}
-            pos[b, h] = [lut[r.tobytes()] for r in k_out[b, h]]
-    return pos
-
-
 @pytest.fixture(scope="module")
 def lib():
     from kvpress_amd import _native
@@ -135,8 +121,7 @@ def oracle_merge(monkeypatch, fake_native):
 
     def merge_values_(keys, values, kept_idx, k_out, v_out, threshold, fraction, target=None, max_sim=None):
         calls.append((tuple(keys.shape), tuple(kept_idx.shape), threshold, fraction))
-        dt = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}[v_out.dtype]
-        o = O.merge(keys.float().numpy(), values.float().numpy(), kept_idx.numpy(), threshold, fraction, dt)
+        o = O.merge(keys.float().numpy(), values.float().numpy(), kept_idx.numpy(), threshold, fraction, dtype_name(v_out.dtype))
         v_out.copy_(torch.from_numpy(o["v"]).to(v_out.dtype))
         return v_out
 
@@ -150,7 +135,7 @@ def oracle_merge(monkeypatch, fake_native):
 def test_compress_on_host_matches_reference(name, order, oracle_merge):
     import kvpress_amd as P
 
-    s, g = MI.make_case(name), _golden(name)
+    s, g = MI.make_case(name), golden(name)
     module, hidden, kw = MI.module_and_kwargs(s, torch.float32)
     keys = torch.from_numpy(s["keys"])
     values = torch.from_numpy(s["values"])
@@ -171,7 +156,7 @@ def test_compress_on_host_matches_reference(name, order, oracle_merge):
         kept = np.take_along_axis(kept, perm, -1)
         ref_v = np.take_along_axis(ref_v, perm[..., None].repeat(s["D"], -1), 2)
         if order == "score":
-            mine = np.argsort(_kept_positions(k2.numpy(), s["keys"]), axis=-1, kind="stable")
+            mine = np.argsort(kept_positions(k2.numpy(), s["keys"]), axis=-1, kind="stable")
             k2 = torch.from_numpy(np.take_along_axis(k2.numpy(), mine[..., None].repeat(s["D"], -1), 2))
             v2 = torch.from_numpy(np.take_along_axis(v2.numpy(), mine[..., None].repeat(s["D"], -1), 2))
     np.testing.assert_array_equal(k2.numpy(), np.take_along_axis(s["keys"], kept[..., None].astype(np.int64).repeat(s["D"], -1), 2))

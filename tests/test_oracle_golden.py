@@ -6,14 +6,10 @@ import numpy as np
 import pytest
 
 import _inputs
+from _support import golden, golden_path
 from oracle import kvpress_oracle as O
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 ALL = list(_inputs.CASES)
-
-
-def load(name):
-    return np.load(os.path.join(GOLD, f"{name}.npz"))
 
 
 def oracle_scores(s, cos=None, sin=None):
@@ -55,7 +51,7 @@ def oracle_scores(s, cos=None, sin=None):
 @pytest.mark.parametrize("name", ALL)
 def test_oracle_scores_match_reference(name):
     s = _inputs.make_case(name)
-    g = load(name)
+    g = golden(name)
     sc = oracle_scores(s)
     ref = g["scores_f32"]
     assert sc.shape == ref.shape == (s["B"], s["H"], s["S"])
@@ -69,7 +65,7 @@ def test_oracle_scores_match_reference(name):
 @pytest.mark.parametrize("name", ALL)
 def test_oracle_topk_matches_reference(name):
     s = _inputs.make_case(name)
-    g = load(name)
+    g = golden(name)
     ref = g["scores_f32"]
     for i, r in enumerate(s["ratios"]):
         if s["kind"] == "pyramid":
@@ -165,7 +161,7 @@ def test_torch_path_is_the_reference_op_for_op(name, torch_path_pinned):
     from oracle.torch_path_pinned import key, record
 
     s = _inputs.make_case(name)
-    g = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "torch_path_pinned.json")))
+    g = json.load(open(golden_path("torch_path_pinned.json")))
     fields = ["scores_f32", "scores_nat"] + [f"{f}_{i}" for i in range(len(s["ratios"])) for f in ("nkept", "idx_f32")]
     got = record({key(name, f): torch_path_pinned[key(name, f)] for f in fields})
     for k, v in got.items():

@@ -5,14 +5,14 @@ the tiny random-init Llama / in-memory tokenizer of tests/_inputs.py.  Here the 
 kvpress_amd.pipeline with this package's presses; on CPU the HIP entry points are replaced by the oracle-backed fakes
 of conftest.py (host logic under test), on the GPU box the real kernels run (marked gpu)."""
 import json
-import os
 
 import pytest
 import torch
 
 import _inputs
+from _support import golden_path
 
-GOLD = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "pipeline.json")))
+PINNED = json.load(open(golden_path("pipeline.json")))
 
 
 
@@ -35,8 +35,8 @@ def _run(name, device="cpu", dtype=None):
 @pytest.mark.parametrize("name", list(_inputs.PIPELINE_CASES))
 def test_pipeline_matches_reference_answers_cpu(name, fake_native):
     res, lengths = _run(name)
-    assert lengths == GOLD[name]["cache_lengths"]      # compressed length, and the answers were removed from the cache
-    assert res["answers"] == GOLD[name]["answers"]
+    assert lengths == PINNED[name]["cache_lengths"]      # compressed length, and the answers were removed from the cache
+    assert res["answers"] == PINNED[name]["answers"]
 
 
 def _run_finch(name, device="cpu", dtype=None):
@@ -47,9 +47,9 @@ def _run_finch(name, device="cpu", dtype=None):
     cache = DynamicCache()
     res, press = _inputs.run_finch_pipeline(kvpress_amd, lambda m, t: pipeline("kv-press-text-generation", model=m, tokenizer=t, device=m.device), name, cache,
                                             dtype=dtype, device=device)
-    assert press.window_size == GOLD[name]["window_size"]
-    assert [int(cache.get_seq_length(i)) for i in range(len(cache))] == GOLD[name]["cache_lengths"]
-    assert res["answers"] == GOLD[name]["answers"]
+    assert press.window_size == PINNED[name]["window_size"]
+    assert [int(cache.get_seq_length(i)) for i in range(len(cache))] == PINNED[name]["cache_lengths"]
+    assert res["answers"] == PINNED[name]["answers"]
 
 
 @pytest.mark.parametrize("name", list(_inputs.FINCH_PIPELINE_CASES))
@@ -67,8 +67,8 @@ def _run_family(name, device="cpu", dtype=None):
                     device=device)
     cache = DynamicCache()
     res = pipe(_inputs.tiny_context(n_words), questions=questions, press=_inputs.build_press(kvpress_amd, spec), max_new_tokens=max_new, cache=cache)
-    assert [int(cache.get_seq_length(i)) for i in range(len(cache))] == GOLD[name]["cache_lengths"]
-    assert res["answers"] == GOLD[name]["answers"]
+    assert [int(cache.get_seq_length(i)) for i in range(len(cache))] == PINNED[name]["cache_lengths"]
+    assert res["answers"] == PINNED[name]["answers"]
 
 
 @pytest.mark.parametrize("name", list(_inputs.FAMILY_PIPELINE_CASES))
@@ -87,7 +87,7 @@ def test_single_question_and_registry(fake_native):
     assert isinstance(pipe, KVPressTextGenerationPipeline)
     spec, n_words, questions, max_new = _inputs.PIPELINE_CASES["pipe_knorm"]
     out = pipe(_inputs.tiny_context(n_words), question=questions[0], press=_inputs.build_press(P, spec), max_new_tokens=max_new)
-    assert out == {"answer": GOLD["pipe_knorm"]["answers"][0]}
+    assert out == {"answer": PINNED["pipe_knorm"]["answers"][0]}
     with pytest.raises(AssertionError):
         pipe("w1 w2", question="w1", questions=["w2"])
 
@@ -149,8 +149,8 @@ def test_context_truncation(fake_native):
 def test_pipeline_matches_reference_answers_gpu(name):
     """Same calls, fp32 model on cuda:0, presses on the HIP kernels."""
     res, lengths = _run(name, device="cuda:0", dtype=torch.float32)
-    assert lengths == GOLD[name]["cache_lengths"]
-    assert res["answers"] == GOLD[name]["answers"]
+    assert lengths == PINNED[name]["cache_lengths"]
+    assert res["answers"] == PINNED[name]["answers"]
 
 
 @pytest.mark.gpu

@@ -1,27 +1,22 @@
 """ThinKPress (key-channel pruning) against the REAL reference's outputs (tests/golden/think_*.npz, oracle/gen_golden_think.py).
 CPU: the oracle restatement and the press's host logic over oracle-backed entry points; GPU (marked): the kernels."""
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import _inputs
+from _support import golden
 from oracle import kvpress_oracle as O
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 NAMES = list(_inputs.THINK_CASES)
 DEV = "cuda:0"
-
-
-def gold(name):
-    return np.load(os.path.join(GOLD, f"{name}.npz"))
 
 
 @pytest.mark.parametrize("name", NAMES)
 def test_oracle_matches_reference(name):
     s = _inputs.make_think_case(name)
-    g = gold(name)
+    g = golden(name)
     sc = O.think_channel_scores(g["qwin_f32"], s["keys"])
     for i, r in enumerate(s["ratios"]):
         idx, k = O.think_prune(s["keys"], sc, r)
@@ -62,7 +57,7 @@ def _run(s, dev, dt):
 @pytest.mark.parametrize("name", NAMES)
 def test_press_matches_reference_cpu(name, fake_native):
     s = _inputs.make_think_case(name)
-    g = gold(name)
+    g = golden(name)
     for i, r, pruned in _run(s, "cpu", torch.float32):
         assert np.array_equal(pruned, g[f"pruned_f32_{i}"]), f"{name} r={r}"
 
@@ -91,7 +86,7 @@ def test_think_kernels_vs_oracle(name):
 
     s = _inputs.make_think_case(name)
     dt = _inputs.torch_dtype(s["dtype"])
-    q = _inputs.round_to(gold(name)["qwin_f32"], s["dtype"])
+    q = _inputs.round_to(golden(name)["qwin_f32"], s["dtype"])
     k = torch.from_numpy(s["keys"]).to(device=DEV, dtype=dt)
     got = _native.think_channel_scores(torch.from_numpy(q).to(device=DEV, dtype=dt), k).cpu().numpy()
     np.testing.assert_allclose(got, O.think_channel_scores(q, s["keys"]), rtol=2e-5, atol=1e-30, err_msg=name)
@@ -111,7 +106,7 @@ def test_think_kernels_vs_oracle(name):
 @pytest.mark.parametrize("name", NAMES)
 def test_press_matches_reference_gpu(name):
     s = _inputs.make_think_case(name)
-    g = gold(name)
+    g = golden(name)
     for i, r, pruned in _run(s, DEV, torch.float32):
         assert np.array_equal(pruned, g[f"pruned_f32_{i}"]), f"{name} r={r}"
     if s["dtype"] != "f32":   # model dtype: the same channels up to near-ties of the 16-bit reference scores

@@ -1,23 +1,21 @@
 """ChunkPress / KeyRerotationPress against the REAL reference's outputs (tests/golden/wrap_*.npz, made by
 oracle/gen_golden_wrappers.py).  CPU: oracle restatement and the host logic of the wrappers over oracle-backed entry
 points; GPU (marked): the same classes on the HIP kernels, plus kernel-level checks of the two new entry points."""
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import _inputs
+from _support import golden
 from oracle import kvpress_oracle as O
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 ADAKV = [n for n, c in _inputs.WRAP_CASES.items() if c["wrapper"] == "adakv"]
 BLOCK = [n for n, c in _inputs.WRAP_CASES.items() if c["wrapper"] == "block"]
 CHUNK = [n for n, c in _inputs.WRAP_CASES.items() if c["wrapper"] == "chunk"]
 CHUNKKV = [n for n, c in _inputs.WRAP_CASES.items() if c["wrapper"] == "chunkkv"]
 REROT = [n for n, c in _inputs.WRAP_CASES.items() if c["wrapper"] == "rerot"]
 DEV = "cuda:0"
-
 
 
 def _pair_rel(got, ref):
@@ -35,10 +33,6 @@ def _elem_rel_no_cancellation(got, ref):
     pn = np.concatenate([pn, pn], axis=-1)
     m = (np.abs(ref) >= 0.5 * pn) & (pn > 1e-3)
     return float((np.abs(got - ref)[m] / np.abs(ref)[m]).max()) if m.any() else 0.0
-
-
-def gold(name):
-    return np.load(os.path.join(GOLD, f"{name}.npz"))
 
 
 def inner_press(s, ratio):
@@ -79,7 +73,7 @@ def oracle_chunk_scores(s, cos=None, sin=None):
 @pytest.mark.parametrize("name", CHUNK)
 def test_oracle_chunk_indices_match_reference(name):
     s = _inputs.make_wrap_case(name)
-    g = gold(name)
+    g = golden(name)
     att, rot, hidden, (cos, sin) = _inputs.build_llama_attention(s, torch.float32)
     fn = oracle_chunk_scores(s, cos.numpy(), sin.numpy())
     for i, r in enumerate(s["ratios"]):
@@ -90,7 +84,7 @@ def test_oracle_chunk_indices_match_reference(name):
 @pytest.mark.parametrize("name", CHUNKKV)
 def test_oracle_chunkkv_indices_match_reference(name):
     s = _inputs.make_wrap_case(name)
-    g = gold(name)
+    g = golden(name)
     sc = _oracle_scores_full(s)
     for i, r in enumerate(s["ratios"]):
         if s["S"] < s["chunk_length"]:   # no complete chunk: the wrapped press's own selection (in torch.topk's order there)
@@ -116,7 +110,7 @@ def test_chunkkv_matches_reference_cpu(name, fake_native):
 @pytest.mark.parametrize("name", REROT)
 def test_oracle_rerotation_matches_reference(name):
     s = _inputs.make_wrap_case(name)
-    g = gold(name)
+    g = golden(name)
     att, rot, hidden, pe = _inputs.build_llama_attention(s, torch.float32)
     inv = rot.inv_freq.numpy()
     for i, r in enumerate(s["ratios"]):
@@ -134,7 +128,7 @@ def test_oracle_rerotation_matches_reference(name):
 
 
 def _run_wrapper(s, name, dev, dt):
-    g = gold(name)
+    g = golden(name)
     att, rot, hidden, pe = _inputs.build_llama_attention(s, dt, dev)
     att.rotary_emb = rot
     keys = torch.from_numpy(s["keys"]).to(device=dev, dtype=dt)
@@ -175,14 +169,14 @@ def _oracle_scores_full(s):
 @pytest.mark.parametrize("name", ADAKV)
 def test_oracle_adakv_matches_reference(name):
     s = _inputs.make_wrap_case(name)
-    g = gold(name)
+    g = golden(name)
     sc = _oracle_scores_full(s)
     for i, r in enumerate(s["ratios"]):
         assert np.array_equal(O.adakv_pruned(sc, r, s["alpha"]), g[f"masked_{i}"]), f"{name} r={r}"
 
 
 def _run_adakv(s, name, dev):
-    g = gold(name)
+    g = golden(name)
     att, rot, hidden, pe = _inputs.build_llama_attention(s, torch.float32, dev)
     att.config._attn_implementation = "sdpa"
     keys = torch.from_numpy(s["keys"]).to(dev)
@@ -362,7 +356,7 @@ def test_rerotation_native_dtype_gpu(name):
     from kvpress_amd import _native
 
     s = _inputs.make_wrap_case(name)
-    g = gold(name)
+    g = golden(name)
     dt = _inputs.torch_dtype(s["dtype"])
     att, rot, hidden, pe = _inputs.build_llama_attention(s, dt, DEV)
     keys = torch.from_numpy(s["keys"]).to(device=DEV, dtype=dt)
