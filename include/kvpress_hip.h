@@ -394,6 +394,27 @@ int kvp_vwl1norm_rescale(const void* values, int64_t v_sb, int64_t v_sh, int64_t
 int kvp_scores_fill_prefix(float* scores, int64_t R, int64_t S, int64_t row_stride, const int32_t* idx, int64_t n, const int32_t* counts,
                            float value, kvp_stream_t stream);
 
+/* ---- KVzipPress.score_kvzip (kvpress/presses/kvzip_press.py:312-332, :350-354; with the scales also :336-337, :348) -------------------
+ * The maximum cross-attention of one context chunk during the "repeat the context" forward.  q: PRE-RoPE queries of the Lq repeated
+ * tokens [B,Hq,Lq,D]; cos / sin: their rotary tables [Bc,Lq,D], Bc = B or 1 (cs_sb = 0 broadcasts), RoPE'd in the library as in
+ * kvp_snapkv_score_rope (:312-313).  k: the layer's keys as they sit in the cache after that forward, [B,Hkv,S,D] with S = context
+ * length + Lq (element strides; no subsampled copy as at :319-327).  0 <= sink <= start < end <= S - Lq.  Row t of query head hG+g sees
+ *     V(t) = [0, sink) u [start, end) u { S - Lq + u : u <= t }
+ * p = softmax over V(t) of q.k / sqrt(D) in float32 (:330-332), and
+ *     out[b,h,j - start] = max over g < G, t < Lq of p[g,t,j] * row_scale[b,t] * col_scale[b,hG+g,j - start]       start <= j < end
+ * (:350-351).  row_scale float32 [B,Lq] and col_scale float32 [B,Hq,end-start], contiguous, non-negative (KVzip+'s 1/||h_t|| and
+ * ||V_j Wo_{h,g}||, :336-337, :348), either may be NULL (= 1).  out: float32, row (b,h) at out + (b*Hkv + h) * out_stride, so a press
+ * writes straight into its score table (:354).  Nothing of extent Lq x keys is stored: pass 1 keeps (max, log-sum) per row over all of
+ * V(t), skipping key tiles above the causal diagonal; pass 2 recomputes the chunk's logits and keeps the column maximum of
+ * 2^(s - lse).  bf16 / f16 with D in {64,96,128,256} and 16-byte aligned key rows run on the matrix cores, everything else (float32,
+ * other even D, unaligned rows) on a generic kernel.  Workspace: the rotated queries + 12 bytes per (b, query head, row) per key split
+ * + the partial maxima.  Bit-identical from run to run (no atomics). */
+size_t kvp_kvzip_score_workspace_bytes(int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t Lq, int64_t D, int64_t sink, int64_t ctx);
+int kvp_kvzip_score(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const void* cos, const void* sin, int64_t cs_sb, int64_t cs_sw,
+                    const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S,
+                    int64_t Lq, int64_t D, int64_t sink, int64_t start, int64_t end, const float* row_scale, const float* col_scale,
+                    float* out, int64_t out_stride, void* ws, size_t ws_bytes, kvp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

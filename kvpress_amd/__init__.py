@@ -65,6 +65,9 @@ def __getattr__(name):
     if name == "CriticalKVPress":      # built, but the top-level name stays refused for now
         raise AttributeError("kvpress_amd has no top-level CriticalKVPress: the name is still listed outside the hot-path scope of this "
                              "package (DESIGN.md section 9); the class lives at kvpress_amd.presses.criticalkv_press.CriticalKVPress")
+    if name == "KVzipPress":           # built, the top-level name likewise still refused
+        raise AttributeError("kvpress_amd has no top-level KVzipPress: the name is still listed outside the hot-path scope of this "
+                             "package (DESIGN.md section 9); the class lives at kvpress_amd.presses.kvzip_press.KVzipPress")
     if name in _NOT_BUILT:
         raise AttributeError(f"kvpress_amd has no {name}: it is outside the hot-path scope of this package (SURVEY.md section 8, DESIGN.md "
                              f"section 9); use NVIDIA/kvpress's {name}")

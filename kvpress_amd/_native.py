@@ -109,6 +109,9 @@ SIGNATURES = {
     "kvp_vwl1norm_rescale": (c_int, [c_void_p, _I64, _I64, _I64, c_int, c_void_p, _I64, _I64, _I64, _I64, _I64, _I64, _I64, c_void_p, _I64,
                                      c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "kvp_scores_fill_prefix": (c_int, [c_void_p, _I64, _I64, _I64, c_void_p, _I64, c_void_p, c_float, c_void_p]),
+    "kvp_kvzip_score_workspace_bytes": (c_size_t, [c_int] + [_I64] * 7),
+    "kvp_kvzip_score": (c_int, [c_void_p, _I64, _I64, _I64, c_void_p, c_void_p, _I64, _I64, c_void_p, _I64, _I64, _I64, c_int, _I64, _I64, _I64,
+                                _I64, _I64, _I64, _I64, _I64, _I64, c_void_p, c_void_p, c_void_p, _I64, c_void_p, c_size_t, c_void_p]),
 }
 # include/kvpress_hip_lab.h: measurement / test aids of the same library (bench.py, tools/, the select's residency tests)
 LAB_SIGNATURES = {
@@ -890,6 +893,41 @@ def scores_fill_prefix_(scores: torch.Tensor, idx: torch.Tensor, counts: torch.T
     with _on_device(scores.device):
         _call("kvp_scores_fill_prefix", _p(scores), R, S, S, _p(idx), n, _p(counts), float(value), _stream(scores))
     return scores
+
+
+# KVzipPress (kvzip_press.py:312-354)
+def kvzip_score(q_pre: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, keys: torch.Tensor, sink: int, start: int, end: int,
+                row_scale: Optional[torch.Tensor] = None, col_scale: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """KVzip's maximum cross-attention of the chunk ``[start, end)``: float32 [B,Hkv,end-start] from the PRE-RoPE queries [B,Hq,Lq,D] of
+    the repeated tokens, their cos / sin [1 or B, Lq, D] and the layer's keys [B,Hkv,S,D] as the cache holds them after that forward (the
+    last Lq rows are the repeated tokens' keys; a strided view passes through).  ``row_scale`` [B,Lq] and ``col_scale`` [B,Hq,end-start]
+    (non-negative) multiply the probabilities before the maximum.  ``out``: a float32 view [B,Hkv,end-start] with a contiguous last
+    dim and rows ``out.stride(1)`` apart (a slice of the press's score table) that is written in place."""
+    keys = _rows(keys)
+    q_pre, B, Hq, Hkv, S, Lq, D = _queries(q_pre, keys)
+    cos, sin = _rotary(cos, sin, keys.dtype, (B, Lq, D))
+    sink, start, end = int(sink), int(start), int(end)
+    n = end - start
+
+    def scale(t, shape):
+        if t is None:
+            return None
+        assert tuple(t.shape) == shape, (t.shape, shape)
+        return _dev(t.to(device=keys.device, dtype=torch.float32)).contiguous()
+
+    row_scale, col_scale = scale(row_scale, (B, Lq)), scale(col_scale, (B, Hq, n))
+    if out is None:
+        out = torch.empty((B, Hkv, max(n, 0)), dtype=torch.float32, device=keys.device)
+    assert out.dtype == torch.float32 and out.device == keys.device and tuple(out.shape) == (B, Hkv, n), (out.shape, out.dtype, (B, Hkv, n))
+    row_stride = out.stride(1) if Hkv > 1 else (out.stride(0) if B > 1 else n)
+    assert (n <= 1 or out.stride(2) == 1) and (B == 1 or out.stride(0) == Hkv * row_stride), out.stride()
+    with _on_device(keys.device):
+        nws = _ws_bytes("kvp_kvzip_score_workspace_bytes", _DTYPES[keys.dtype], B, Hq, Hkv, Lq, D, sink, n)
+        ws = _ws(nws, keys)
+        _call("kvp_kvzip_score", *_tensor(q_pre), *_tables(cos, sin), *_tensor(keys), _DTYPES[keys.dtype], B, Hq, Hkv, S, Lq, D, sink, start, end,
+              _p(row_scale), _p(col_scale), _p(out), row_stride, _p(ws), ws.numel(), _stream(keys))
+    return out
 
 
 # ---- the q_proj eligibility logic ---------------------------------------------------------------------------------------------------

@@ -35,7 +35,9 @@ FILE_FLAGS = {"snapkv_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "ea_mfma.
               # vwl1.hip: the abs-sum reads all 16 accumulators with the |x| source modifier.  Left to itself the SLP vectoriser packs
               # those adds into v_pk_add_f32 behind v_and masks (more instructions beside the MFMAs, not fewer) and the D = 128
               # kernel then spills at two waves per SIMD.
-              "vwl1.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"]}
+              "vwl1.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
+              # kvzip.hip: both epilogues (running softmax statistics, column maximum) read every accumulator with VALU ops
+              "kvzip.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def flags_for(src: str):

@@ -21,9 +21,10 @@ class ComposedPress(BasePress):
     def __post_init__(self):
         self.compression_ratio = None
         from kvpress_amd.presses.adakv_press import AdaKVPress
+        from kvpress_amd.presses.kvzip_press import KVzipPress
 
-        # the reference's own rule (composed_press.py:47-50; KVzipPress is not part of this package)
-        assert not any(isinstance(press, AdaKVPress) for press in self.presses), "ComposedPress cannot contains AdaKVPress or KVzipPress"
+        # the reference's own rule (composed_press.py:47-50)
+        assert not any(isinstance(press, (AdaKVPress, KVzipPress)) for press in self.presses), "ComposedPress cannot contains AdaKVPress or KVzipPress"
         self._order_checked = False
 
     def _check_kept_order(self):
