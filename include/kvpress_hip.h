@@ -16,7 +16,7 @@
  *     (sb, sh, ss) so sliced cache views (keys[:, :, n_sink:], chunk slices) need no copy;
  *   - outputs and workspaces are caller-allocated; *_workspace_bytes() gives the size;
  *   - every call is asynchronous on `stream` (a hipStream_t), allocates no device memory, never
- *     synchronises (kvp_leverage_status excepted) and is thread-safe;
+ *     synchronises (kvp_leverage_status and kvp_threshold_count excepted) and is thread-safe;
  *   - process-wide state, created on first use and kept until exit: one host-pinned status word
  *     (kvp_async_error_check below) and, per device, a stream guard that orders the one-launch
  *     select of long rows ("one cluster select per device" at kvp_topk_select);
@@ -414,6 +414,36 @@ int kvp_kvzip_score(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, con
                     const void* k, int64_t k_sb, int64_t k_sh, int64_t k_ss, int dtype, int64_t B, int64_t Hq, int64_t Hkv, int64_t S,
                     int64_t Lq, int64_t D, int64_t sink, int64_t start, int64_t end, const float* row_scale, const float* col_scale,
                     float* out, int64_t out_stride, void* ws, size_t ws_bytes, kvp_stream_t stream);
+
+/* ---- KVzapPress.score (kvpress/presses/kvzap_press.py:79-81; the surrogate's bodies :33-35 linear, :38-45 mlp) --------------------------
+ * x: the hidden states the attention layer received, [B,S,K] (element strides x_sb, x_ss; rows contiguous).  w1 [N,K], b1 [N], w2 [Hout,N],
+ * b2 [Hout]: one layer of KVzapModel.layers, contiguous, in x's dtype.  N == 0 is the linear model: w1 is [Hout,K], b1 its bias, w2 / b2
+ * are ignored.
+ *     mlp:    out[b,o,s] = b2[o] + sum_j w2[o,j] * gelu(b1[j] + sum_k x[b,s,k] * w1[j,k])          linear: out[b,o,s] = b1[o] + sum_k x w1[o,k]
+ * out: float32 [B,Hout,S] through element strides (the transpose of :81 is part of the store).  Layer one accumulates in float32, the bias
+ * is added in float32, the GELU is the erf form in float32 (nn.GELU()), layer two is float32 fmas over the unrounded activations in a
+ * fixed order.  bf16 / f16 with 16-byte aligned rows, K % 32 == 0 and Hout <= 16: more than 16 tokens run on the matrix cores (N % 32 == 0,
+ * 32 <= N <= 1024: a workgroup owns a tile of tokens and all N hidden columns, nothing of extent S x N is stored; the linear model on an
+ * mma16 kernel bound by reading x once); up to 16 tokens (a decoding step) spread the rows of w1 over the chip, write float32 partials per
+ * slice into the workspace and add them in slice order in a second launch.  Everything else (float32, unaligned rows, other K / N,
+ * Hout <= 256) runs on a generic kernel.  S == 0 succeeds and writes nothing.  Bit-identical from run to run (no atomics). */
+size_t kvp_kvzap_score_workspace_bytes(int dtype, int64_t B, int64_t S, int64_t K, int64_t N, int64_t Hout);
+int kvp_kvzap_score(const void* x, int64_t x_sb, int64_t x_ss, int dtype, const void* w1, const void* b1, const void* w2, const void* b2,
+                    int64_t B, int64_t S, int64_t K, int64_t N, int64_t Hout, float* out, int64_t o_sb, int64_t o_sh, int64_t o_ss,
+                    void* ws, size_t ws_bytes, kvp_stream_t stream);
+
+/* ---- DMSPress's eviction (kvpress/presses/dms_press.py:106-112): torch.where(scores < threshold) and the shift ---------------------------
+ * scores: float32 [B,H,n] through element strides (a [..., :n] view of the press's buffer passes as it is).  Phase 1, kvp_threshold_count:
+ * the number of entries with score < threshold (a NaN compares false: kept) into *total, a HOST address -- the call waits for the
+ * stream, as the reference's torch.where does -- and the per-block offsets into the workspace.  Phase 2, kvp_threshold_select, with the
+ * same arguments, that workspace and that total: out_b / out_h / out_p int64 [total] receive (b, h, position + shift) of those entries
+ * in row-major order (torch.where's), ready for module.masked_key_indices.  No atomics; n = 1 and n = 131072 take the same kernels. */
+size_t kvp_threshold_select_workspace_bytes(int64_t B, int64_t H, int64_t n);
+int kvp_threshold_count(const float* scores, int64_t s_sb, int64_t s_sh, int64_t s_sn, int64_t B, int64_t H, int64_t n, float threshold,
+                        void* ws, size_t ws_bytes, int64_t* total, kvp_stream_t stream);
+int kvp_threshold_select(const float* scores, int64_t s_sb, int64_t s_sh, int64_t s_sn, int64_t B, int64_t H, int64_t n, float threshold,
+                         int64_t shift, const void* ws, size_t ws_bytes, int64_t total, int64_t* out_b, int64_t* out_h, int64_t* out_p,
+                         kvp_stream_t stream);
 
 #ifdef __cplusplus
 }

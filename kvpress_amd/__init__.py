@@ -20,6 +20,7 @@ from kvpress_amd.presses.finch_press import FinchPress
 from kvpress_amd.presses.key_rerotation_press import KeyRerotationPress
 from kvpress_amd.presses.keydiff_press import KeyDiffPress
 from kvpress_amd.presses.knorm_press import KnormPress
+from kvpress_amd.presses.kvzap_press import KVzapPress
 from kvpress_amd.presses.leverage_press import LeverageScorePress
 from kvpress_amd.presses.merging_press import MergingPress
 from kvpress_amd.presses.non_causal_attention_press import NonCausalAttnPress
@@ -35,11 +36,11 @@ from kvpress_amd.presses.tova_press import TOVAPress
 __version__ = "0.1.0"
 # the path (a), the scorers that reuse its kernels (f-2), the selection wrappers (f-3), the decode-time step (f-4), the
 # pipeline (f-1); plus four tiny host-only presses the reference's own test fixtures for those rows are built from (Composed, PerLayer,
-# Random, StreamingLLM); plus the Compactor family (NonCausalAttn, LeverageScore, Compactor), MergingPress, CAMPress and CriticalAdaKVPress.  Presses outside that scope that still have kernels here live in kvpress_amd.contrib.
+# Random, StreamingLLM); plus the Compactor family (NonCausalAttn, LeverageScore, Compactor), MergingPress, CAMPress, CriticalAdaKVPress and KVzapPress.  Presses outside that scope that still have kernels here live in kvpress_amd.contrib.
 __all__ = ["BasePress", "ScorerPress", "KnormPress", "SnapKVPress", "ExpectedAttentionPress", "PyramidKVPress", "TOVAPress", "KeyDiffPress", "QFilterPress",
            "CURPress", "FinchPress", "ChunkPress", "KeyRerotationPress", "AdaKVPress", "DecodingPress", "CompressionRatioDecodingPress", "PrefillDecodingPress",
            "ComposedPress", "PerLayerCompressionPress", "RandomPress", "StreamingLLMPress", "KVPressTextGenerationPipeline",
-           "NonCausalAttnPress", "LeverageScorePress", "CompactorPress", "MergingPress", "CAMPress", "CriticalAdaKVPress"]
+           "NonCausalAttnPress", "LeverageScorePress", "CompactorPress", "MergingPress", "CAMPress", "CriticalAdaKVPress", "KVzapPress"]
 
 
 # The reference exports every press at top level (kvpress/__init__.py:7-49).  The five out-of-scope presses that exist here resolve
@@ -47,7 +48,7 @@ __all__ = ["BasePress", "ScorerPress", "KnormPress", "SnapKVPress", "ExpectedAtt
 # package importing its contrib sub-package); the reference's other presses are NOT part of this package and say so.
 _CONTRIB = ("BlockPress", "ChunkKVPress", "LagKVPress", "ObservedAttentionPress", "ThinKPress")
 _NOT_BUILT = ("CapPress", "CriticalKVPress", "DMSPress", "DuoAttentionPress",
-              "ExpectedAttentionStatsPress", "FastKVzipPress", "KVComposePress", "KVzapPress", "KVzipPress", "LUKVPress",
+              "ExpectedAttentionStatsPress", "FastKVzipPress", "KVComposePress", "KVzipPress", "LUKVPress",
               "RestoreKVPress", "SimLayerKVPress")
 
 
@@ -68,6 +69,9 @@ def __getattr__(name):
     if name == "KVzipPress":           # built, the top-level name likewise still refused
         raise AttributeError("kvpress_amd has no top-level KVzipPress: the name is still listed outside the hot-path scope of this "
                              "package (DESIGN.md section 9); the class lives at kvpress_amd.presses.kvzip_press.KVzipPress")
+    if name == "DMSPress":             # built (it drives KVzapPress), the top-level name likewise still refused
+        raise AttributeError("kvpress_amd has no top-level DMSPress: the name is still listed outside the hot-path scope of this "
+                             "package (DESIGN.md section 9); the class lives at kvpress_amd.presses.dms_press.DMSPress")
     if name in _NOT_BUILT:
         raise AttributeError(f"kvpress_amd has no {name}: it is outside the hot-path scope of this package (SURVEY.md section 8, DESIGN.md "
                              f"section 9); use NVIDIA/kvpress's {name}")

@@ -112,6 +112,13 @@ SIGNATURES = {
     "kvp_kvzip_score_workspace_bytes": (c_size_t, [c_int] + [_I64] * 7),
     "kvp_kvzip_score": (c_int, [c_void_p, _I64, _I64, _I64, c_void_p, c_void_p, _I64, _I64, c_void_p, _I64, _I64, _I64, c_int, _I64, _I64, _I64,
                                 _I64, _I64, _I64, _I64, _I64, _I64, c_void_p, c_void_p, c_void_p, _I64, c_void_p, c_size_t, c_void_p]),
+    "kvp_kvzap_score_workspace_bytes": (c_size_t, [c_int] + [_I64] * 5),
+    "kvp_kvzap_score": (c_int, [c_void_p, _I64, _I64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, _I64, _I64, _I64, _I64, _I64,
+                                c_void_p, _I64, _I64, _I64, c_void_p, c_size_t, c_void_p]),
+    "kvp_threshold_select_workspace_bytes": (c_size_t, [_I64] * 3),
+    "kvp_threshold_count": (c_int, [c_void_p, _I64, _I64, _I64, _I64, _I64, _I64, c_float, c_void_p, c_size_t, ctypes.POINTER(c_int64), c_void_p]),
+    "kvp_threshold_select": (c_int, [c_void_p, _I64, _I64, _I64, _I64, _I64, _I64, c_float, _I64, c_void_p, c_size_t, _I64,
+                                     c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 # include/kvpress_hip_lab.h: measurement / test aids of the same library (bench.py, tools/, the select's residency tests)
 LAB_SIGNATURES = {
@@ -927,6 +934,49 @@ def kvzip_score(q_pre: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, keys:
         ws = _ws(nws, keys)
         _call("kvp_kvzip_score", *_tensor(q_pre), *_tables(cos, sin), *_tensor(keys), _DTYPES[keys.dtype], B, Hq, Hkv, S, Lq, D, sink, start, end,
               _p(row_scale), _p(col_scale), _p(out), row_stride, _p(ws), ws.numel(), _stream(keys))
+    return out
+
+
+def kvzap_score(hidden_states: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: Optional[torch.Tensor] = None,
+                b2: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """KVzap's surrogate scores (kvzap_press.py:79-81): float32 [B,Hout,S] from the hidden states [B,S,K] (rows contiguous, any strides
+    over B and S) and one layer of the surrogate, contiguous and in the hidden states' dtype: ``w1`` [N,K], ``b1`` [N], ``w2`` [Hout,N],
+    ``b2`` [Hout] for the mlp; ``w1`` [Hout,K], ``b1`` [Hout] and no second layer for the linear model.  ``out``: a float32 [B,Hout,S]
+    tensor of any strides that is written in place."""
+    x = _rows(hidden_states)
+    B, S, K = x.shape
+    mlp = w2 is not None
+    for t in (w1, b1) + ((w2, b2) if mlp else ()):
+        assert t is not None and t.dtype == x.dtype and t.device == x.device and t.is_contiguous(), "surrogate weights: contiguous, in the hidden states' dtype, on their device"
+    N, Hout = (w1.shape[0], w2.shape[0]) if mlp else (0, w1.shape[0])
+    assert w1.shape[1] == K and b1.numel() == w1.shape[0] and (not mlp or (w2.shape[1] == N and b2.numel() == Hout)), (x.shape, w1.shape, b1.shape)
+    if out is None:
+        out = torch.empty((B, Hout, S), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.device == x.device and tuple(out.shape) == (B, Hout, S), (out.shape, out.dtype, (B, Hout, S))
+    with _on_device(x.device):
+        ws = _ws(_ws_bytes("kvp_kvzap_score_workspace_bytes", _DTYPES[x.dtype], B, S, K, N, Hout), x)
+        _call("kvp_kvzap_score", *_tensor(x, 2), _DTYPES[x.dtype], _p(w1), _p(b1), _p(w2), _p(b2), B, S, K, N, Hout, *_tensor(out),
+              _p(ws), ws.numel(), _stream(x))
+    return out
+
+
+def threshold_select(scores: torch.Tensor, threshold: float, shift: int = 0) -> list:
+    """``list(torch.where(scores < threshold))`` with ``shift`` added to the positions (dms_press.py:106-112): three int64 tensors
+    (batch, head, position + shift) in row-major order for float32 scores [B,H,n] of any strides.  A NaN is not below the threshold.
+    Waits for the stream once, to size the result, as torch.where does."""
+    if not scores.is_cuda:
+        raise KvpressHipError(f"kvpress_amd kernels need tensors on a HIP device, got {scores.device} (no CPU fallback exists)")
+    assert scores.dtype == torch.float32 and scores.dim() == 3, (scores.dtype, scores.shape)
+    B, H, n = scores.shape
+    total = c_int64(0)
+    with _on_device(scores.device):
+        st = _stream(scores)
+        ws = _ws(_ws_bytes("kvp_threshold_select_workspace_bytes", B, H, n), scores)
+        _call("kvp_threshold_count", *_tensor(scores), B, H, n, float(threshold), _p(ws), ws.numel(), ctypes.byref(total), st)
+        out = [torch.empty(total.value, dtype=torch.int64, device=scores.device) for _ in range(3)]
+        if total.value:
+            _call("kvp_threshold_select", *_tensor(scores), B, H, n, float(threshold), int(shift), _p(ws), ws.numel(), total.value,
+                  _p(out[0]), _p(out[1]), _p(out[2]), st)
     return out
 
 

@@ -37,7 +37,9 @@ FILE_FLAGS = {"snapkv_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "ea_mfma.
               # kernel then spills at two waves per SIMD.
               "vwl1.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
               # kvzip.hip: both epilogues (running softmax statistics, column maximum) read every accumulator with VALU ops
-              "kvzip.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+              "kvzip.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+              # kvzap.hip: the epilogue (bias, GELU, layer two) reads and rewrites every accumulator
+              "kvzap.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def flags_for(src: str):
