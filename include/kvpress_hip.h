@@ -445,6 +445,28 @@ int kvp_threshold_select(const float* scores, int64_t s_sb, int64_t s_sh, int64_
                          int64_t shift, const void* ws, size_t ws_bytes, int64_t total, int64_t* out_b, int64_t* out_h, int64_t* out_p,
                          kvp_stream_t stream);
 
+/* ---- FastKVzipPress's gate (kvpress/presses/fastkvzip_press.py:54-71) and the protected positions of :240-247 -----------------------------
+ * x: the hidden states the attention layer received, [B,S,K] (element strides x_sb, x_ss; rows contiguous).  One layer's FastKVzipGate in
+ * its natural layouts: wq [Hkv*G*D, K] and bq [Hkv*G*D] (q_proj), wk [Hkv*D, K] (k_proj, no bias), b [Hkv,G], contiguous, in x's dtype;
+ * gq [D], gk [D] (the RMSNorm weights) and k_base [Hkv,J,D], contiguous float32.  With RMSNorm_g(v) = g * v / sqrt(mean(v^2) + eps):
+ *     q[s,h,g,:] = RMSNorm_gq(x[s] wq[(hG+g)D .. +D]^T + bq[..])              k[s,h,:] = RMSNorm_gk(x[s] wk[hD .. +D]^T)
+ *     logit = <k[s,h], q[s,h,g]> / sqrt(D) + b[h,g]                           base_j = <k_base[h,j], q[s,h,g]> / sqrt(D)
+ *     out[b,h,s] = (1/G) sum_g 1 / (1 + sum_{j<J} exp(base_j - logit))        (J == 0: exactly 1)
+ * and out[b,h,s] = 1.0f exactly for s < protect_head or s >= S - protect_tail (either count may exceed S), written by the same launch.
+ * out: float32 [B,Hkv,S] through element strides, so a press writes each layer into its slice of one [L,B,Hkv,S] table.  The products
+ * accumulate in float32 and everything after them is float32 (the reference rounds the projections and the normalised vectors to the
+ * gate's dtype); every sum has one fixed order (d, then j, then g), no atomics: bit-identical from run to run.  bf16 / f16 with 16-byte
+ * aligned rows, K % 32 == 0, D == 16, J <= 16 and G <= 8 run on the matrix cores: a workgroup owns a tile of 128 tokens and all
+ * (G+1)*16 projected columns of a group of kv heads, so neither q [S, Hkv*G*D] nor the logits [Hkv,S,J,G] are ever stored.  Everything
+ * else (float32, unaligned rows, other K, D <= 64, any J and G with (G+1)*D <= 8192) runs on a generic kernel.  S == 0 succeeds and
+ * writes nothing.  ws / ws_bytes are RESERVED: no path stores anything outside its workgroups' LDS today, the size query returns 0 and the
+ * arguments are not read (ws may be NULL); they are in the signature so that a path that needs scratch can be added without a new entry. */
+size_t kvp_fastkvzip_score_workspace_bytes(int dtype, int64_t B, int64_t S, int64_t K, int64_t Hkv, int64_t G, int64_t D, int64_t J);
+int kvp_fastkvzip_score(const void* x, int64_t x_sb, int64_t x_ss, int dtype, const void* wq, const void* bq, const void* wk, const void* b,
+                        const float* gq, const float* gk, const float* k_base, int64_t B, int64_t S, int64_t K, int64_t Hkv, int64_t G,
+                        int64_t D, int64_t J, float eps, int64_t protect_head, int64_t protect_tail, float* out, int64_t o_sb, int64_t o_sh,
+                        int64_t o_ss, void* ws, size_t ws_bytes, kvp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

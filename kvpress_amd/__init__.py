@@ -16,6 +16,7 @@ from kvpress_amd.presses.criticalkv_press import CriticalAdaKVPress
 from kvpress_amd.presses.cur_press import CURPress
 from kvpress_amd.presses.decoding_press import CompressionRatioDecodingPress, DecodingPress, PrefillDecodingPress
 from kvpress_amd.presses.expected_attention_press import ExpectedAttentionPress
+from kvpress_amd.presses.fastkvzip_press import FastKVzipPress
 from kvpress_amd.presses.finch_press import FinchPress
 from kvpress_amd.presses.key_rerotation_press import KeyRerotationPress
 from kvpress_amd.presses.keydiff_press import KeyDiffPress
@@ -36,11 +37,11 @@ from kvpress_amd.presses.tova_press import TOVAPress
 __version__ = "0.1.0"
 # the path (a), the scorers that reuse its kernels (f-2), the selection wrappers (f-3), the decode-time step (f-4), the
 # pipeline (f-1); plus four tiny host-only presses the reference's own test fixtures for those rows are built from (Composed, PerLayer,
-# Random, StreamingLLM); plus the Compactor family (NonCausalAttn, LeverageScore, Compactor), MergingPress, CAMPress, CriticalAdaKVPress and KVzapPress.  Presses outside that scope that still have kernels here live in kvpress_amd.contrib.
+# Random, StreamingLLM); plus the Compactor family (NonCausalAttn, LeverageScore, Compactor), MergingPress, CAMPress, CriticalAdaKVPress, KVzapPress and FastKVzipPress.  Presses outside that scope that still have kernels here live in kvpress_amd.contrib.
 __all__ = ["BasePress", "ScorerPress", "KnormPress", "SnapKVPress", "ExpectedAttentionPress", "PyramidKVPress", "TOVAPress", "KeyDiffPress", "QFilterPress",
            "CURPress", "FinchPress", "ChunkPress", "KeyRerotationPress", "AdaKVPress", "DecodingPress", "CompressionRatioDecodingPress", "PrefillDecodingPress",
            "ComposedPress", "PerLayerCompressionPress", "RandomPress", "StreamingLLMPress", "KVPressTextGenerationPipeline",
-           "NonCausalAttnPress", "LeverageScorePress", "CompactorPress", "MergingPress", "CAMPress", "CriticalAdaKVPress", "KVzapPress"]
+           "NonCausalAttnPress", "LeverageScorePress", "CompactorPress", "MergingPress", "CAMPress", "CriticalAdaKVPress", "KVzapPress", "FastKVzipPress"]
 
 
 # The reference exports every press at top level (kvpress/__init__.py:7-49).  The five out-of-scope presses that exist here resolve
@@ -48,7 +49,7 @@ __all__ = ["BasePress", "ScorerPress", "KnormPress", "SnapKVPress", "ExpectedAtt
 # package importing its contrib sub-package); the reference's other presses are NOT part of this package and say so.
 _CONTRIB = ("BlockPress", "ChunkKVPress", "LagKVPress", "ObservedAttentionPress", "ThinKPress")
 _NOT_BUILT = ("CapPress", "CriticalKVPress", "DMSPress", "DuoAttentionPress",
-              "ExpectedAttentionStatsPress", "FastKVzipPress", "KVComposePress", "KVzipPress", "LUKVPress",
+              "ExpectedAttentionStatsPress", "KVComposePress", "KVzipPress", "LUKVPress",
               "RestoreKVPress", "SimLayerKVPress")
 
 

@@ -119,6 +119,10 @@ SIGNATURES = {
     "kvp_threshold_count": (c_int, [c_void_p, _I64, _I64, _I64, _I64, _I64, _I64, c_float, c_void_p, c_size_t, ctypes.POINTER(c_int64), c_void_p]),
     "kvp_threshold_select": (c_int, [c_void_p, _I64, _I64, _I64, _I64, _I64, _I64, c_float, _I64, c_void_p, c_size_t, _I64,
                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    "kvp_fastkvzip_score_workspace_bytes": (c_size_t, [c_int] + [_I64] * 7),
+    "kvp_fastkvzip_score": (c_int, [c_void_p, _I64, _I64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    _I64, _I64, _I64, _I64, _I64, _I64, _I64, c_float, _I64, _I64, c_void_p, _I64, _I64, _I64,
+                                    c_void_p, c_size_t, c_void_p]),
 }
 # include/kvpress_hip_lab.h: measurement / test aids of the same library (bench.py, tools/, the select's residency tests)
 LAB_SIGNATURES = {
@@ -977,6 +981,35 @@ def threshold_select(scores: torch.Tensor, threshold: float, shift: int = 0) -> 
         if total.value:
             _call("kvp_threshold_select", *_tensor(scores), B, H, n, float(threshold), int(shift), _p(ws), ws.numel(), total.value,
                   _p(out[0]), _p(out[1]), _p(out[2]), st)
+    return out
+
+
+def fastkvzip_score(hidden_states: torch.Tensor, wq: torch.Tensor, bq: torch.Tensor, wk: torch.Tensor, b: torch.Tensor, gq: torch.Tensor,
+                    gk: torch.Tensor, k_base: torch.Tensor, eps: float, protect_head: int = 0, protect_tail: int = 0,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """FastKVzip's gate scores (fastkvzip_press.py:54-71, :240-247): float32 [B,Hkv,S] from the hidden states [B,S,K] (rows contiguous,
+    any strides over B and S) and one layer's gate: ``wq`` [Hkv*G*D,K], ``bq`` [Hkv*G*D], ``wk`` [Hkv*D,K] and ``b`` [Hkv,G] contiguous in
+    the hidden states' dtype; the norm weights ``gq``, ``gk`` [D] and ``k_base`` [Hkv,J,D] contiguous float32.  The first
+    ``protect_head`` and the last ``protect_tail`` positions are written as exactly 1.0.  ``out``: a float32 [B,Hkv,S] tensor of any
+    strides (a layer's slice of the press's score table) that is written in place."""
+    x = _rows(hidden_states)
+    B, S, K = x.shape
+    for t in (wq, bq, wk, b):
+        assert t.dtype == x.dtype and t.device == x.device and t.is_contiguous(), "gate projections and b: contiguous, in the hidden states' dtype, on their device"
+    for t in (gq, gk, k_base):
+        assert t.dtype == torch.float32 and t.device == x.device and t.is_contiguous(), "norm weights and k_base: contiguous float32 on the hidden states' device"
+    Hkv, G = b.shape
+    D = gq.numel()
+    J = k_base.shape[1]
+    assert wq.shape == (Hkv * G * D, K) and bq.numel() == Hkv * G * D and wk.shape == (Hkv * D, K) and gk.numel() == D and \
+        tuple(k_base.shape) == (Hkv, J, D), (x.shape, wq.shape, bq.shape, wk.shape, b.shape, gq.shape, gk.shape, k_base.shape)
+    if out is None:
+        out = torch.empty((B, Hkv, S), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.device == x.device and tuple(out.shape) == (B, Hkv, S), (out.shape, out.dtype, (B, Hkv, S))
+    with _on_device(x.device):
+        ws = _ws(_ws_bytes("kvp_fastkvzip_score_workspace_bytes", _DTYPES[x.dtype], B, S, K, Hkv, G, D, J), x)
+        _call("kvp_fastkvzip_score", *_tensor(x, 2), _DTYPES[x.dtype], _p(wq), _p(bq), _p(wk), _p(b), _p(gq), _p(gk), _p(k_base), B, S, K, Hkv, G,
+              D, J, float(eps), int(protect_head), int(protect_tail), *_tensor(out), _p(ws), ws.numel(), _stream(x))
     return out
 
 

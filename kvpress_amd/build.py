@@ -39,7 +39,9 @@ FILE_FLAGS = {"snapkv_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "ea_mfma.
               # kvzip.hip: both epilogues (running softmax statistics, column maximum) read every accumulator with VALU ops
               "kvzip.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
               # kvzap.hip: the epilogue (bias, GELU, layer two) reads and rewrites every accumulator
-              "kvzap.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+              "kvzap.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+              # fastkvzip.hip: the epilogue (bias, two RMSNorms, the dot products) reads and rewrites every accumulator
+              "fastkvzip.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 
 def flags_for(src: str):

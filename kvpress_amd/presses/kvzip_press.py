@@ -30,6 +30,34 @@ from kvpress_amd.utils import _is_quantized, extract_keys_and_values, get_prerop
 logger = logging.getLogger(__name__)
 
 
+def mask_lowest_scores(model, score_val: torch.Tensor, compression_ratio: float, layerwise: bool) -> None:
+    """``compress_post`` of KVzipPress (:360-394) and of FastKVzipPress (fastkvzip_press.py:251-287), which share it line for line: from
+    the score table [L, B, Hkv, S] the cross-layer budget, then each layer's bottom-k across heads into ``module.masked_key_indices``."""
+    if compression_ratio > 0:
+        n_layer, bsz, num_key_value_heads, ctx_len = score_val.shape
+
+        if layerwise:
+            n_pruned_layers = [int(bsz * num_key_value_heads * ctx_len * compression_ratio)] * n_layer
+        else:   # once per context: a torch expression
+            n_pruned_indices = int(score_val.numel() * compression_ratio)
+            pruned_indices = torch.topk(-score_val.reshape(-1), n_pruned_indices).indices
+            n_tokens_per_layer = bsz * num_key_value_heads * ctx_len
+            n_pruned_layers = torch.bincount(pruned_indices // n_tokens_per_layer, minlength=n_layer).tolist()
+
+        for layer in model.model.layers:
+            module = layer.self_attn
+            layer_idx = int(module.layer_idx)
+            assert module.config._attn_implementation != "eager", "eager mode not supported"
+
+            scores = score_val[layer_idx]
+            n_pruned = int(n_pruned_layers[layer_idx])
+            flat = _native.topk_select(scores.view(bsz, num_key_value_heads * ctx_len), n_pruned,
+                                       _native.ORDER_POSITION | _native.TOPK_SMALLEST)
+            flat = flat.to(torch.int64).flatten()
+            batch_indices = torch.arange(bsz, device=flat.device).repeat_interleave(n_pruned)
+            module.masked_key_indices = (batch_indices, flat // ctx_len, flat % ctx_len)
+
+
 @dataclass
 class KVzipPress(BasePress):
     """KVzip (https://arxiv.org/abs/2505.23416).
@@ -237,26 +265,4 @@ class KVzipPress(BasePress):
 
     def compress_post(self, model):
         """The (head, position) pairs every layer masks (:360-394): the cross-layer budget, then each layer's bottom-k across heads."""
-        if self.compression_ratio > 0:
-            n_layer, bsz, num_key_value_heads, ctx_len = self.score_val.shape
-
-            if self.layerwise:
-                n_pruned_layers = [int(bsz * num_key_value_heads * ctx_len * self.compression_ratio)] * n_layer
-            else:   # once per context: a torch expression
-                n_pruned_indices = int(self.score_val.numel() * self.compression_ratio)
-                pruned_indices = torch.topk(-self.score_val.reshape(-1), n_pruned_indices).indices
-                n_tokens_per_layer = bsz * num_key_value_heads * ctx_len
-                n_pruned_layers = torch.bincount(pruned_indices // n_tokens_per_layer, minlength=n_layer).tolist()
-
-            for layer in model.model.layers:
-                module = layer.self_attn
-                layer_idx = int(module.layer_idx)
-                assert module.config._attn_implementation != "eager", "eager mode not supported"
-
-                scores = self.score_val[layer_idx]
-                n_pruned = int(n_pruned_layers[layer_idx])
-                flat = _native.topk_select(scores.view(bsz, num_key_value_heads * ctx_len), n_pruned,
-                                           _native.ORDER_POSITION | _native.TOPK_SMALLEST)
-                flat = flat.to(torch.int64).flatten()
-                batch_indices = torch.arange(bsz, device=flat.device).repeat_interleave(n_pruned)
-                module.masked_key_indices = (batch_indices, flat // ctx_len, flat % ctx_len)
+        mask_lowest_scores(model, self.score_val, self.compression_ratio, self.layerwise)
